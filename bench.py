@@ -30,8 +30,21 @@ BENCH_PREWARM_S = 0.1 s (the count from one timed step, the slowest rank's, so e
 same steps), so the clocks are up after the host's checks — a barrier + device sync, exactly K timed
 steps, device sync + barrier; the max over ranks.
 
+A plain run does what the headline needs and no more: it generates the layer, uploads it, warms up
+(the warmup's counts checked against the generator's plan), times the K steps and prints the line
+(value, ms_per_step, the timed region's own kernel events and their roofline).  --full adds every
+other leg: the results checked against host references and the oracle, the per-kernel breakdown of a
+step (three more steps with events around every launch), the fallback-sort / arena / heads / presorted
+variants, the CPU baselines and the host pack / H2D timings (each of them can be switched off with
+its own --no-... option, as before).
+
+--dump-outputs DIR: after the timed steps, what the last of them left — the arrays a caller of the
+timed path receives — as DIR/<name>.npy (float64).  An output longer than its share of 64 MB is cut
+to a fixed, seeded sample of its rows.  The inputs are seeded, so two builds of the library run
+with the same arguments can be compared output for output.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c5env|c6] [--n UNITS]
-                       [--no-cpu-baseline] [--no-host-timing]
+                       [--full [--no-cpu-baseline] [--no-host-timing]] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -72,8 +85,13 @@ def parse():
     ap.add_argument("--n", type=int, default=0,
                     help="units (c3: polygons of the whole layer, 100M; c2: points per GPU, 10M; c4: rows, 50M; "
                          "c5: features of the filtered layer, 100M; c5env/c6: geometries, 20M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-timing", action="store_true", help="skip the host pack / H2D timings")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: reference checks of the results, the per-kernel breakdown, the "
+                         "fallback / arena / heads / presorted variants, CPU baselines and host timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-host-timing", action="store_true", help="--full: skip the host pack / H2D timings")
     ap.add_argument("--unordered", action="store_true",
                     help="c2/c3: tile-grouped delta list (per-tile atomic appends, no k_place2); default: key order")
     ap.add_argument("--sort-gather", action="store_true",
@@ -111,6 +129,8 @@ def parse():
     if not a.n:
         a.n = {"c2": 10_000_000, "c3": 100_000_000, "c3v": 100_000_000, "c4": 50_000_000, "c5": 100_000_000, "c5env": 20_000_000,
                "c6": 20_000_000}[a.workload]
+    if not a.full:  # a plain run: the headline's own setup, warmup and timed steps only
+        a.no_cpu_baseline = a.no_host_timing = a.no_sort = a.no_radix = a.no_arena_timing = a.no_heads_path = True
     if a.traffic_json is None:
         for d in PROFILE_ROUNDS + ("",):  # the newest PMC passes of the workload
             a.traffic_json = os.path.join(ROOT, "profiles", d, f"traffic_{a.workload}.json")
@@ -129,6 +149,62 @@ def host_cores():
     except AttributeError:
         c = os.cpu_count() or 1
     return max(1, min(c, 16))  # the GPU box's CPU share is 16 cores (nproc shows the whole host)
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 0x44554D50
+
+
+def dump_outputs(args, H, arrays):
+    """--dump-outputs: ``arrays`` {name: array} — what the last timed step left, as its caller receives
+    it — as DIR/<name>.npy in float64 (rank r > 0 of a multi-GPU run: DIR/<name>.rank<r>.npy).  Every
+    array gets an equal share of DUMP_BYTES; one with more rows than fit is cut to a seeded choice of
+    its rows (ascending, a function of the row count alone), so equal outputs give equal files."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1)
+        rows = max(1, share // (8 * (a.shape[1] if a.ndim > 1 else 1)))
+        if a.shape[0] > rows:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], rows, replace=False))]
+        f = a.astype(np.float64)
+        assert np.array_equal(f.astype(a.dtype), a), f"{name}: values do not fit float64 exactly"
+        suffix = f".rank{H.rank}" if H.rank else ""
+        np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), f)
+
+
+def polygons_layer_joined(n, same_len):
+    """synth.polygons_layer(n) — the whole C3 layer — generated as bucket-range shards on the host
+    cores and joined.  The shards are contiguous runs of the tree walk that tile it, every entry and
+    blob a function of its pk alone (tests/test_synth_c3.py), so the arrays equal the one-piece
+    call's; numpy releases the GIL inside its loops, so the threads do run side by side."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from kart_amd import packing, synth
+
+    cores = host_cores()
+    parts = 4 * cores
+    with ThreadPoolExecutor(cores) as ex:
+        S = list(ex.map(lambda r: synth.polygons_layer(n, shard=(r, parts), same_len=same_len), range(parts)))
+
+        def offsets(offs):  # the shards' arena offsets, each rebased behind the shards before it
+            at = np.cumsum([0] + [int(o[-1]) for o in offs[:-1]])
+            return np.concatenate([np.zeros(1, np.uint64)] + [o[1:] + np.uint64(b) for o, b in zip(offs, at)])
+
+        jobs = []
+        for side, blobs in (("base", "base_blobs"), ("target", "target_blobs")):
+            jobs += [ex.submit(np.concatenate, [getattr(s, side).key for s in S]),
+                     ex.submit(np.concatenate, [getattr(s, side).oid for s in S]),
+                     ex.submit(np.concatenate, [getattr(s, blobs)[0] for s in S]),
+                     ex.submit(offsets, [getattr(s, blobs)[1] for s in S])]
+        got = [j.result() for j in jobs]
+    sides = [packing.PackedSide(key=k, oid=o, key_mode=0, order=np.arange(k.shape[0], dtype=np.int64),
+                                encoding=packing.INT_PK_ENCODING) for k, o in (got[0:2], got[4:6])]
+    return synth.Layer(sides[0], sides[1], (got[2], got[3]), (got[6], got[7]), S[0].schema, S[0].legends,
+                       sum(s.n_insert for s in S), sum(s.n_update for s in S), sum(s.n_delete for s in S))
 
 
 class Harness:
@@ -318,8 +394,9 @@ def run_diff(args, H, polygons):
     split = polygons and world > 1  # C3: one layer split by bucket range (strong scaling)
     t0 = time.time()
     if polygons:
-        L = synth.polygons_layer(n, shard=(rank, world) if split else None,
-                                 same_len=args.same_len if args.workload == "c3v" else 0.0)
+        same_len = args.same_len if args.workload == "c3v" else 0.0
+        L = synth.polygons_layer(n, shard=(rank, world), same_len=same_len) if split else \
+            polygons_layer_joined(n, same_len)
     else:
         L = synth.points_layer(n, seed=synth.SEED + rank, pk0=shard.rank_pk_base(rank, n))
     gen_s = time.time() - t0
@@ -353,7 +430,7 @@ def run_diff(args, H, polygons):
     if not args.no_check:
         assert (counts["inserts"], counts["updates"], counts["deletes"]) == plan, (counts, plan)
         assert not status.any(), "fielddiff status flags set"
-        if pipe.pk_order:  # the pk-ordered records: a stable argsort of the records' pks
+        if args.full and pipe.pk_order:  # the pk-ordered records: a stable argsort of the records' pks
             check_pk_order(pipe, L, delta, upd)
     if split:
         mx = max(x for x in H.allgather(counts["deltas"]))
@@ -375,16 +452,25 @@ def run_diff(args, H, polygons):
     total_pairs = sum(H.allgather(n_pairs))
     total_deltas = sum(H.allgather(counts["deltas"]))
     kern = kernel_times(eng, ("k_partition2", "k_join2", "k_place2", "k_fielddiff", "k_rebase"))
-    # every kernel of the step once more with events around each launch (untimed steps): the parts
-    eng.prof_reset()
-    eng.prof_select(None)
-    eng.prof_enable(True)
-    for _ in range(3):
-        pipe.step()
-    eng.sync()
-    eng.prof_enable(False)
-    parts = kernel_times(eng, STEP_KERNELS)
-    pk_sort = pk_sort_summary(pipe, parts, counts) if pipe.pk_order else None
+    if args.dump_outputs:  # the last timed step's results, as DiffPipeline hands them to its caller
+        c, d_delta, d_upd, d_masks, d_status = pipe.results()
+        arrays = {"counts": np.array([c["inserts"], c["updates"], c["deletes"], c["deltas"]]), "delta": d_delta,
+                  "upd": d_upd, "masks": d_masks, "status": d_status}
+        if pipe.pk_order:
+            arrays.update(zip(("delta_pk", "delta_pk_perm", "upd_pk", "upd_pk_perm"), pipe.pk_results()))
+        dump_outputs(args, H, arrays)
+        del arrays, d_delta, d_upd, d_masks, d_status
+    parts, pk_sort, pk_ordered = {}, None, pipe.pk_order
+    if args.full:  # every kernel of the step once more with events around each launch (untimed steps): the parts
+        eng.prof_reset()
+        eng.prof_select(None)
+        eng.prof_enable(True)
+        for _ in range(3):
+            pipe.step()
+        eng.sync()
+        eng.prof_enable(False)
+        parts = kernel_times(eng, STEP_KERNELS)
+        pk_sort = pk_sort_summary(pipe, parts, counts) if pipe.pk_order else None
     sort = None
     if not args.no_sort and not split:  # the fallback: sides in a non-key order, both GPU side sorts in the step
         del pipe
@@ -433,7 +519,7 @@ def run_diff(args, H, polygons):
         "config": {"workload": wl, "features": n if polygons else n * world, "pairs_per_step": total_pairs,
                    "deltas_per_step": total_deltas, "updates_per_step": sum(H.allgather(counts["updates"])),
                    "delta_order": "tile-grouped (same delta set)" if args.unordered else
-                   ("walk (= key) order, then pk order (kd_delta_pk_order)" if pk_sort else "walk (= key) order"),
+                   ("walk (= key) order, then pk order (kd_delta_pk_order)" if pk_ordered else "walk (= key) order"),
                    "side_order": "git tree (walk) order as listed, no side sort",
                    "blob_arenas": ("per-entry arenas read through the join's update pairs" if args.pair_arenas else
                                    "update-order arenas (the drop-in's form: update i's blobs at index i; the field "
@@ -441,11 +527,12 @@ def run_diff(args, H, polygons):
                    "parallelism": f"bucket-range shards x{world}" + (", RCCL all-gather of counts + delta records"
                                                                       if split else "")},
         "kernels_avg_ms": {k: round(v[1], 5) for k, v in kern.items()},
-        "step_kernels_avg_ms": {k: round(v[1], 5) for k, v in parts.items()},
-        "step_kernel_launches": {k: v[0] // 3 for k, v in parts.items()},
         "roofline": roof,
         "cpu_baseline": cpu,
     }
+    if args.full:
+        out["step_kernels_avg_ms"] = {k: round(v[1], 5) for k, v in parts.items()}
+        out["step_kernel_launches"] = {k: v[0] // 3 for k, v in parts.items()}
     if pk_sort:
         out["pk_order"] = pk_sort
     if sort:
@@ -811,15 +898,24 @@ def run_c5(args, H):
     elapsed = timed(H, eng, pipe.step, args.steps)
     eng.prof_enable(False)
     kern = kernel_times(eng, ("k_partition2", "k_join2", "k_place2", kname, "k_gf_scan", "k_gf_place"))
-    eng.prof_reset()
-    eng.prof_select(None)
-    eng.prof_enable(True)
-    for _ in range(3):
-        pipe.step()
-    eng.sync()
-    eng.prof_enable(False)
-    parts = kernel_times(eng, ("k_partition2", "k_join2", "k_gscan2", "k_place2", "k_gh_gather", kname, "k_gf_scan",
-                               "k_gf_place"))
+    if args.dump_outputs:  # the last timed step's results, as FilterPipeline hands them to its caller
+        c, d_delta, d_codes, d_keep, d_enc, d_ok = pipe.results()
+        dump_outputs(args, H, {"counts": np.array([c["inserts"], c["updates"], c["deletes"], c["deltas"], c["kept"]]),
+                               "delta": d_delta, "codes": d_codes, "keep": d_keep, "enc_ok": d_ok,
+                               # (an index envelope is written only where enc_ok says so)
+                               "enc": np.where(d_ok[:, None] == 1, d_enc, 0) if d_enc is not None else d_ok[:0]})
+        del d_delta, d_codes, d_keep, d_enc, d_ok
+    parts = {}
+    if args.full:  # every kernel of the step with events around each launch (untimed steps)
+        eng.prof_reset()
+        eng.prof_select(None)
+        eng.prof_enable(True)
+        for _ in range(3):
+            pipe.step()
+        eng.sync()
+        eng.prof_enable(False)
+        parts = kernel_times(eng, ("k_partition2", "k_join2", "k_gscan2", "k_place2", "k_gh_gather", kname, "k_gf_scan",
+                                   "k_gf_place"))
     n_pairs = L.base.n + L.n_insert
     total_pairs = sum(H.allgather(n_pairs))
     nd = counts["deltas"]
@@ -1027,6 +1123,11 @@ def run_c5env(args, H):
     eng.prof_enable(False)
     total = sum(H.allgather(n))
     kern = kernel_times(eng, ("k_envelopes", "k_env_overlap"))
+    if args.dump_outputs:  # the last timed step's flags, index envelopes (where enc_ok) and overlap flags
+        d_ok = ok.download(np.uint8, n)
+        dump_outputs(args, H, {"match": match.download(np.uint8, n), "enc_ok": d_ok,
+                               "overlap": np.where(d_ok == 1, ovl.download(np.uint8, n), 0),
+                               "enc": np.where(d_ok[:, None] == 1, enc.download(np.uint8, n * nb).reshape(n, nb), 0)})
     npt = int(is_pt.sum())
     # algorithmic bytes per k_envelopes launch: offsets (8 B) + GPKG header (8 B) + stored envelope
     # (32 B, polygons) or point WKB (21 B) read; match + enc_ok flags (2 B) + encoded envelope written
@@ -1166,9 +1267,10 @@ def run_c6(args, H):
     for _ in range(max(1, args.warmup)):
         step()
     eng.sync()
-    O = oracle()
-    if not args.no_check:  # every geometry is valid LE GPKG; sampled strings equal the oracle's
+    if not args.no_check:  # every geometry is valid LE GPKG
         assert int(status.download(np.uint8, n).max()) == 0, "kd_hex_encode flagged a valid geometry"
+    O = oracle() if args.full else None
+    if args.full and not args.no_check:  # sampled strings equal the oracle's
         st = start.download(np.uint32, n)
         for i in list(range(0, n, max(1, n // 2000))) + [n - 1]:
             o, e = int(off[i]), int(off[i + 1])
@@ -1182,6 +1284,16 @@ def run_c6(args, H):
     eng.prof_enable(False)
     total = sum(H.allgather(n))
     kern = kernel_times(eng, ("k_hex", "k_wkb_start"))
+    if args.dump_outputs:  # the last timed step's status, WKB starts and hex characters (from each WKB's start on)
+        d_st = start.download(np.uint32, n)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, 1000), replace=False))
+        hexes = np.zeros((pick.size, 2 * int(np.diff(off).max())), np.uint8)  # one zero-padded row per picked geometry
+        for r, i in enumerate(pick.tolist()):
+            a, e = 2 * (int(off[i]) + int(d_st[i])), 2 * int(off[i + 1])
+            if e > a:
+                hexes[r, :e - a] = hexbuf.download(np.uint8, e - a, offset=a)
+        dump_outputs(args, H, {"status": status.download(np.uint8, n), "wkb_start": d_st, "hex_geometry": pick,
+                               "hex": hexes})
     # algorithmic bytes per k_hex launch: the geometry arena read once, two hex chars written per byte
     roof = roofline(kern, "k_hex", 3 * nbytes, args.traffic_json, n, "c6")
     cpu = None
@@ -1280,7 +1392,7 @@ def run_c4(args, H):
     n_clean, conf, md = pipe.results()
     srt = []
     for S, order in zip((A, O_, T), pipe.orders()):
-        if not args.no_check:  # the per-bucket sorts == a full sort of the keys
+        if args.full and not args.no_check:  # the per-bucket sorts == a full sort of the keys
             ko = S.key[order]
             assert np.all(ko[1:] > ko[:-1]), "segmented sort: keys not ascending"
         srt.append((S.key[order], S.oid[order], order))
@@ -1294,14 +1406,21 @@ def run_c4(args, H):
     nall = A.n + O_.n + T.n
     total = sum(H.allgather(nall))
     kern = kernel_times(eng, C4_KERNELS)
-    eng.prof_reset()
-    eng.prof_select(None)
-    eng.prof_enable(True)
-    for _ in range(3):
-        pipe.step()
-    eng.sync()
-    eng.prof_enable(False)
-    parts = kernel_times(eng, C4_KERNELS)
+    if args.dump_outputs:  # the last timed step's results, as MergePipeline hands them to its caller
+        d_clean, d_conf, d_md = pipe.results()
+        dump_outputs(args, H, {"n_clean": np.array([d_clean]), "conflicts": d_conf, "merge_deltas": d_md,
+                               **{f"order_{k}": o for k, o in zip(("ancestor", "ours", "theirs"), pipe.orders())}})
+        del d_conf, d_md
+    parts = {}
+    if args.full:  # every kernel of the step with events around each launch (untimed steps)
+        eng.prof_reset()
+        eng.prof_select(None)
+        eng.prof_enable(True)
+        for _ in range(3):
+            pipe.step()
+        eng.sync()
+        eng.prof_enable(False)
+        parts = kernel_times(eng, C4_KERNELS)
     # classify3 in one pass (k_join3b): dominant kernel k_join3, algorithmic bytes per
     # launch — what the join must read with the sides in walk order (late materialisation):
     #   per ours / theirs entry: key 8 + OID 20 + walk row 4 B, and its filename;

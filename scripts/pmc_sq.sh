@@ -7,7 +7,7 @@ WL=${WL:-c3}
 OUT=$R/gpurun_out/sq_$TAG
 mkdir -p $OUT
 [ -n "$LIB" ] && export KART_AMD_LIB=$R/$LIB
-ARGS="--workload $WL ${N:+--n $N} --steps 3 --warmup 1 --no-cpu-baseline --no-host-timing --no-sort $BENCH_EXTRA"
+ARGS="--full --workload $WL ${N:+--n $N} --steps 3 --warmup 1 --no-cpu-baseline --no-host-timing --no-sort $BENCH_EXTRA"
 export TMPDIR=/tmp
 cd /tmp
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS"

@@ -10,7 +10,7 @@ R=$(pwd)
 TAG=${1:-r02}
 WL=${WL:-c3}
 KERN=${KERN:-k_fielddiff}
-ARGS=${BENCH_ARGS:-"--workload $WL --steps 5 --warmup 1 --no-cpu-baseline --no-host-timing"}
+ARGS=${BENCH_ARGS:-"--full --workload $WL --steps 5 --warmup 1 --no-cpu-baseline --no-host-timing"}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
