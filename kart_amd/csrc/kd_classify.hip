@@ -462,7 +462,6 @@ int kd_reserve(kd_ctx* ctx, uint64_t max_entries_per_side, uint64_t max_updates)
     if ((rc = ensure(ctx, "c2.tcnt", ntiles * 16, &p))) return rc;
     if ((rc = ensure(ctx, "c2.gsum", 2 * (ntiles / 64 + 1) * 8, &p))) return rc;
     if ((rc = ensure(ctx, "c2.sdel", ntiles * (C2_TILE + 64) * 8, &p))) return rc;
-    if ((rc = ensure(ctx, "c2.supd", ntiles * (C2_TILE + 64) * 8, &p))) return rc;
     (void)max_updates;
     return KD_OK;
 }

@@ -9,10 +9,12 @@
 // Default (key-ordered) path:
 //   k_join2    one tile per 256-thread workgroup: keys by LDS-DMA into LDS, branch-free 4-ary split
 //              search + register walk, OIDs of matched pairs compared straight from HBM, ballot
-//              compaction into the tile's staging slot + tile counts + 64-tile group sums;
+//              compaction of the deltas into the tile's staging slot + tile counts + 64-tile group
+//              sums (the delta list only: the updates are the deltas with both indices present);
 //   k_gscan2   one block: exclusive prefix of the 64-tile group sums, and the totals
 //   k_place2   one wave per tile: its group's prefix + earlier tiles of its group -> offset, staged
-//              records -> final key-ordered positions.
+//              records -> final key-ordered positions; the update list derived on the way (a ballot
+//              rank per 64-record chunk + a running count), so it is never staged.
 // KD_DIFF_UNORDERED: k_join2 appends each tile's records at an atomically reserved offset (tiles in
 // completion order, key order inside each tile); no k_place2.
 // (Earlier variants — a persistent register-prefetched join, a decoupled look-back and a per-wave
@@ -156,14 +158,12 @@ struct Join2Args {
     const u8* dummy;     // >= 16 readable device bytes: source of masked-off chunk loads
     const u32* ordA;     // PERM: row of sorted entry i in the OID (and filename-offset) arrays
     const u32* ordB;
-    uint2* stage_delta;  // staged path: tile-local slots of TILE records
-    uint2* stage_upd;
+    uint2* stage_delta;  // staged path: tile-local slots of TILE records (the updates are derived by k_place2)
     u32* tile_cnt;       // staged path: [ntiles*4] inserts, updates, deletes, deltas
     u64* gsum;           // staged path: [2*ngroups] deltas | updates<<32, inserts | deletes<<32
     uint2* out_delta;    // final lists
     uint2* out_upd;
-    u64* stage_dkey;     // (optional) the join key of every staged delta / update record
-    u64* stage_ukey;
+    u64* stage_dkey;     // (optional) the join key of every staged delta record
     u64* out_dkey;       // (optional) the key of every delta / update, beside the final lists
     u64* out_ukey;
     u64* counts;         // [4] inserts, updates, deletes, deltas
@@ -459,6 +459,8 @@ __device__ __forceinline__ TileCounts tile_counts(const u32 rec[IPT], u32* s_wav
     return c;
 }
 
+// the staged path passes su = ku = nullptr (k_place2 derives the updates from the delta list); the
+// unordered path writes both lists where they belong
 template <int IPT>
 __device__ __forceinline__ void tile_write(const u32 rec[IPT], const TileCounts& c, u64 i0, u64 j0,
                                            uint2* __restrict__ sd, uint2* __restrict__ su, const u64* sA, const u64* sB,
@@ -626,8 +628,8 @@ __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
     }
     if (bad) atomicOr(g.err, 1u);
     const TileCounts c = tile_counts<NT, IPT>(rec, s_wave);
-    uint2 *sd, *su;
-    u64 *kd, *ku;
+    uint2 *sd, *su = nullptr;
+    u64 *kd, *ku = nullptr;
     if (UNORD) {
         // four lanes of wave 0 reserve in parallel: deltas, updates (offsets) + inserts, deletes
         if (tid < 4) {
@@ -642,10 +644,8 @@ __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
         kd = g.out_dkey ? g.out_dkey + s_base[0] : nullptr;
         ku = g.out_dkey && g.out_upd && g.out_ukey ? g.out_ukey + s_base[1] : nullptr;  // each key list optional
     } else {
-        sd = g.stage_delta + tile * (u64)C2_STAGE;
-        su = g.stage_upd + tile * (u64)C2_STAGE;
+        sd = g.stage_delta + tile * (u64)C2_STAGE;  // the delta list only: k_place2 derives the updates
         kd = g.stage_dkey ? g.stage_dkey + tile * (u64)C2_STAGE : nullptr;
-        ku = g.stage_dkey ? g.stage_ukey + tile * (u64)C2_STAGE : nullptr;
     }
     tile_write<IPT>(rec, c, q.i0, q.j0, sd, su, sA, sB, kd, ku);
     if (!UNORD && tid == 0) {
@@ -773,10 +773,8 @@ __global__ __launch_bounds__(NT) void k_join2r(Join2Args g) {
         if (bad) atomicOr(g.err, 1u);
         const TileCounts c = tile_counts<NT, IPT, true>(rec, s_wave);
         uint2* sd = g.stage_delta + tile * (u64)C2_STAGE;
-        uint2* su = g.stage_upd + tile * (u64)C2_STAGE;
         u64* kd = g.stage_dkey ? g.stage_dkey + tile * (u64)C2_STAGE : nullptr;
-        u64* ku = g.stage_dkey ? g.stage_ukey + tile * (u64)C2_STAGE : nullptr;
-        tile_write<IPT>(rec, c, q.i0, q.j0, sd, su, sA, sB, kd, ku);
+        tile_write<IPT>(rec, c, q.i0, q.j0, sd, nullptr, sA, sB, kd, nullptr);
         if (tid == 0) {
             u32* cc = g.tile_cnt + 4 * tile;
             const u32 tins = c.tnd - c.tnu - c.tdel;
@@ -865,28 +863,28 @@ __global__ __launch_bounds__(1024) void k_gscan2(const u64* __restrict__ gsum, u
 // Staged path, step 2: tile-local staging -> final key-ordered positions; one tile per block.  The
 // tile's output offset = its group's prefix (k_gscan2) + the counts of the earlier tiles of its own
 // group.  tile_cnt = inserts, updates, deletes, deltas per tile.
+// The update list is the delta list filtered by "both indices present", in the same order: the join
+// stages the deltas only and each update's place is derived here — its rank among the tile's updates
+// from a ballot per 64-record chunk (chunk-major r = j * 64 + lane is key order) plus a running count.
 template <int NT>
-__global__ __launch_bounds__(NT) void k_place2(const uint2* __restrict__ stage_delta, const uint2* __restrict__ stage_upd,
-                                               const u32* __restrict__ tile_cnt, const u64* __restrict__ gpre,
-                                               int tile_items, uint2* __restrict__ out_delta, uint2* __restrict__ out_upd,
-                                               const u64* __restrict__ stage_dkey, const u64* __restrict__ stage_ukey,
-                                               u64* __restrict__ out_dkey, u64* __restrict__ out_ukey) {
+__global__ __launch_bounds__(NT) void k_place2(const uint2* __restrict__ stage_delta, const u32* __restrict__ tile_cnt,
+                                               const u64* __restrict__ gpre, int tile_items,
+                                               uint2* __restrict__ out_delta, uint2* __restrict__ out_upd,
+                                               const u64* __restrict__ stage_dkey, u64* __restrict__ out_dkey,
+                                               u64* __restrict__ out_ukey) {
     static_assert(NT == 64, "k_place2: one wave per tile");
     const int tid = threadIdx.x;
     const u64 t = blockIdx.x;
     const u64 grp = t / C2_GROUP;
     const u64 t_lo = grp * C2_GROUP;
     const uint2* sdp = stage_delta + t * (u64)tile_items;
-    const uint2* sup = stage_upd + t * (u64)tile_items;
-    // The first 64 staged records of both lists are loaded with the counts, before anything is known
-    // about them (a tile's slot is always allocated whole; ~51 deltas and ~41 updates per tile at
-    // 10 % edits): one memory round trip for most tiles instead of two
+    // The first 64 staged records are loaded with the counts, before anything is known about them (a
+    // tile's slot is always allocated whole; ~51 deltas per tile at 10 % edits): one memory round
+    // trip for most tiles instead of two
     const uint2 v0 = sdp[tid];
-    const uint2 w0 = out_upd ? sup[tid] : make_uint2(0, 0);
-    // (and the first 64 record keys of each list, when asked for: no second round trip for them)
+    // (and their keys, when asked for: no second round trip for them)
     const u64* skd = out_dkey ? stage_dkey + t * (u64)tile_items : nullptr;
-    const u64* sku = out_dkey && out_upd && out_ukey ? stage_ukey + t * (u64)tile_items : nullptr;
-    const u64 kd0 = skd ? skd[tid] : 0, ku0 = sku ? sku[tid] : 0;
+    const u64 kd0 = skd ? skd[tid] : 0;
     u64 pd = 0, pu = 0;
     if (tid < (int)(t - t_lo)) {
         const uint4 c = *(const uint4*)(tile_cnt + 4 * (t_lo + tid));
@@ -899,40 +897,38 @@ __global__ __launch_bounds__(NT) void k_place2(const uint2* __restrict__ stage_d
     for (int o = 32; o > 0; o >>= 1) { pd += __shfl_xor(pd, o, 64); pu += __shfl_xor(pu, o, 64); }
     pd += gd;
     pu += gu;
-    const uint2 own = make_uint2(ownc.w, ownc.y);  // (deltas, updates) of this tile
-    constexpr int UC = C2_TILE / NT;
-    uint2 v[UC];
+    // (the tile's delta count, wave-uniform: the chunk loop below runs whole waves through the ballots)
+    const u32 nd = (u32)__builtin_amdgcn_readfirstlane((int)ownc.w);
+    const bool ukeys = out_dkey && out_upd && out_ukey;
+    u32 urun = 0;  // updates of the tile's earlier chunks
+    auto emit = [&](u32 r, const uint2 v, const u64 k) {
+        const bool ok = r < nd;
+        const bool isu = ok && v.x != KD_NONE && v.y != KD_NONE;
+        const u64 bu = __ballot(isu);
+        const u32 ur = urun + __builtin_amdgcn_mbcnt_hi((u32)(bu >> 32), __builtin_amdgcn_mbcnt_lo((u32)bu, 0));
+        urun += (u32)__popcll(bu);
+        if (ok) out_delta[pd + r] = v;
+        if (isu && out_upd) out_upd[pu + ur] = v;
+        if (ok && out_dkey) out_dkey[pd + r] = k;  // the records' keys, when the caller asked for them
+        if (isu && ukeys) out_ukey[pu + ur] = k;
+    };
+    emit((u32)tid, v0, kd0);
+    // later chunks (a tile of more than 64 deltas), four at a time with every load issued before any use
+    for (u32 r0 = NT; r0 < nd; r0 += 4 * NT) {
+        uint2 v[4];
+        u64 kk[4];
 #pragma unroll
-    for (int j = 1; j < UC; j++) {
-        const u32 r = j * NT + tid;
-        if (r < own.x) v[j] = sdp[r];
-    }
-    if ((u32)tid < own.x) out_delta[pd + tid] = v0;
-#pragma unroll
-    for (int j = 1; j < UC; j++) {
-        const u32 r = j * NT + tid;
-        if (r < own.x) out_delta[pd + r] = v[j];
-    }
-    if (out_upd) {
-#pragma unroll
-        for (int j = 1; j < UC; j++) {
-            const u32 r = j * NT + tid;
-            if (r < own.y) v[j] = sup[r];
+        for (int j = 0; j < 4; j++) {
+            const u32 r = r0 + j * NT + tid;
+            v[j] = make_uint2(KD_NONE, KD_NONE);
+            kk[j] = 0;
+            if (r < nd) {
+                v[j] = sdp[r];
+                if (skd) kk[j] = skd[r];
+            }
         }
-        if ((u32)tid < own.y) out_upd[pu + tid] = w0;
 #pragma unroll
-        for (int j = 1; j < UC; j++) {
-            const u32 r = j * NT + tid;
-            if (r < own.y) out_upd[pu + r] = v[j];
-        }
-    }
-    if (skd) {  // the records' keys, when the caller asked for them
-        if ((u32)tid < own.x) out_dkey[pd + tid] = kd0;
-        for (u32 r = tid + NT; r < own.x; r += NT) out_dkey[pd + r] = skd[r];
-    }
-    if (sku) {
-        if ((u32)tid < own.y) out_ukey[pu + tid] = ku0;
-        for (u32 r = tid + NT; r < own.y; r += NT) out_ukey[pu + r] = sku[r];
+        for (int j = 0; j < 4; j++) emit(r0 + j * NT + tid, v[j], kk[j]);
     }
 }
 
@@ -1856,10 +1852,10 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
     g.hash_mode = hash ? 1 : 0;
     g.dummy = (const u8*)dz;
     g.ordA = (const u32*)P(ordO, nO); g.ordB = (const u32*)P(ordT, nT);
-    g.stage_delta = g.stage_upd = nullptr;
+    g.stage_delta = nullptr;
     g.tile_cnt = (u32*)tcnt; g.gsum = (u64*)gsum; g.err = d_err;
     g.out_delta = g.out_upd = nullptr; g.counts = d_counts;
-    g.stage_dkey = g.stage_ukey = g.out_dkey = g.out_ukey = nullptr;
+    g.stage_dkey = g.out_dkey = g.out_ukey = nullptr;
     g.ntiles = ntiles;
     a.K = kK; a.oidK = (const u8*)P(K.oid, nK); a.nameK = (const u8*)P(K.name, nK);
     a.nameOffK = (const u64*)P(K.name_off, nK); a.ordK = (const u32*)P(ordK, nK); a.nK = nK;
@@ -1929,7 +1925,7 @@ int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32
         KD_HIP(hipMemsetAsync(d_counts, 0, 4 * sizeof(u64), ctx->stream));
         return KD_OK;
     }
-    void *part, *tcnt = nullptr, *sdel = nullptr, *supd = nullptr, *gsum = nullptr, *gpre = nullptr;
+    void *part, *tcnt = nullptr, *sdel = nullptr, *gsum = nullptr, *gpre = nullptr;
     int rc;
     if ((rc = ensure(ctx, "c2.part", (ntiles + 1) * sizeof(u64), &part))) return rc;
     u64* zero = nullptr;
@@ -1940,14 +1936,10 @@ int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32
         if ((rc = ensure(ctx, "c2.gsum", n_zero * sizeof(u64), &gsum))) return rc;
         if ((rc = ensure(ctx, "c2.gpre", n_zero * sizeof(u64), &gpre))) return rc;
         if ((rc = ensure(ctx, "c2.sdel", ntiles * C2_STAGE * sizeof(uint2), &sdel))) return rc;
-        if ((rc = ensure(ctx, "c2.supd", ntiles * C2_STAGE * sizeof(uint2), &supd))) return rc;
         zero = (u64*)gsum;
     }
-    void *skd = nullptr, *sku = nullptr;
-    if (d_dkey && !unord) {
-        if ((rc = ensure(ctx, "c2.skd", ntiles * C2_STAGE * sizeof(u64), &skd))) return rc;
-        if ((rc = ensure(ctx, "c2.sku", ntiles * C2_STAGE * sizeof(u64), &sku))) return rc;
-    }
+    void* skd = nullptr;  // the staged records' keys
+    if (d_dkey && !unord && (rc = ensure(ctx, "c2.skd", ntiles * C2_STAGE * sizeof(u64), &skd))) return rc;
     void* dz;
     if ((rc = device_zeros(ctx, &dz))) return rc;
     const u64* kA = nA ? A->key : (const u64*)dz;  // an empty side points at device zeros
@@ -1982,10 +1974,10 @@ int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32
     const int j2r_occ = j2r ? occupancy(ctx, (const void*)k_join2r<C2_NT, C2_IPT>, C2_NT, 0) : 1;
     g.ordA = nA && ordA ? ordA : (const u32*)dz;
     g.ordB = nB && ordB ? ordB : (const u32*)dz;
-    g.stage_delta = (uint2*)sdel; g.stage_upd = (uint2*)supd;
+    g.stage_delta = (uint2*)sdel;
     g.tile_cnt = (u32*)tcnt; g.gsum = (u64*)gsum; g.err = d_err;
     g.out_delta = (uint2*)d_delta; g.out_upd = (uint2*)d_upd; g.counts = d_counts;
-    g.stage_dkey = (u64*)skd; g.stage_ukey = (u64*)sku;
+    g.stage_dkey = (u64*)skd;
     g.out_dkey = d_dkey; g.out_ukey = d_upd ? d_ukey : nullptr;
     g.ntiles = ntiles;
     rc = launch(ctx, "k_join2", [&] {
@@ -2015,9 +2007,8 @@ int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32
     if (rc) return rc;
     return launch(ctx, "k_place2", [&] {
         hipLaunchKernelGGL((k_place2<KD_PLACE_NT>), dim3((unsigned)ntiles), dim3(KD_PLACE_NT), 0, ctx->stream,
-                           (const uint2*)sdel, (const uint2*)supd, (const u32*)tcnt, (const u64*)gpre,
-                           (int)C2_STAGE, (uint2*)d_delta, (uint2*)d_upd, (const u64*)skd, (const u64*)sku, d_dkey,
-                           d_upd ? d_ukey : nullptr);
+                           (const uint2*)sdel, (const u32*)tcnt, (const u64*)gpre, (int)C2_STAGE, (uint2*)d_delta,
+                           (uint2*)d_upd, (const u64*)skd, d_dkey, d_upd ? d_ukey : nullptr);
     });
 }
 
