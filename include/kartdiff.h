@@ -151,7 +151,16 @@ int kd_set_stream(kd_ctx* ctx, void* hip_stream);
  *   fd_stream      [KD_FD_STREAM]      -1 auto, 0 windowed, 1 streamed field diff (contiguous arenas)
  *   fd_walk        [KD_FD_WALK]        -1 / 0 off, 1 the walked field diff (A/B)
  *   pkm_max_blocks [KD_PKM_MAX_BLOCKS] largest pk range (64-pk blocks) kd_delta_pk_order places by bitmap
- *   trace_host     [KD_TRACE_HOST]     1: stream-synced wall-clock marks of host phases to stderr */
+ *   trace_host     [KD_TRACE_HOST]     1: stream-synced wall-clock marks of host phases to stderr
+ *   step_overlap   [KD_STEP_OVERLAP]   kd_diff2_step's schedule: 0 every kernel on the context's stream, in
+ *                                      the order of the separate calls; 1 / 2: the placement and the pk order
+ *                                      on a side stream beside the field diff, which is queued first (1) or
+ *                                      after them (2).  Default 1
+ *   step_overlap_min [KD_STEP_OVERLAP_MIN] the side stream is used from this many entries of both sides
+ *                                      together (2^26: below, the two cross-stream waits cost more than a
+ *                                      short field diff hides)
+ *   pkm_wave       [KD_PKM_WAVE]       the bitmap pk order's scans in their LDS-free one-wave-per-chunk form:
+ *                                      -1 on kd_diff2_step's side stream only, 0 never, 1 always */
 int kd_set_option(kd_ctx* ctx, const char* name, int64_t value);
 int kd_get_option(kd_ctx* ctx, const char* name, int64_t* value);
 int kd_sync(kd_ctx* ctx);
@@ -392,6 +401,53 @@ int kd_sort_segmented_into(kd_ctx* ctx, const uint64_t* d_key_in, uint64_t* d_ke
 int kd_delta_pk_order(kd_ctx* ctx, const kd_side* base, const kd_side* target, const uint32_t* d_delta,
                       const uint64_t* d_keys, uint64_t cap, const uint64_t* d_n, int64_t pk_lo, int64_t pk_hi,
                       int64_t* d_pk, uint32_t* d_perm);
+
+/* -------- the whole step in one call -------- */
+/* kd_diff2_device_ex, kd_fielddiff (device form, the update count read from d_counts[1]) and
+ * kd_delta_pk_order of the deltas and of the updates, with those calls' arguments:
+ *   the join       base, target, base_order / target_order (both or NULL), flags, d_delta, d_upd (optional),
+ *                  d_delta_key / d_upd_key (optional), d_counts, d_err
+ *   the field diff old_blobs NULL: none.  d_pairs NULL: update u's blobs at index u of both arenas; else the
+ *                  device update pairs (d_upd).  upd_cap bounds the update count (0 = unknown); maps,
+ *                  d_masks, d_status as kd_fielddiff's
+ *   the pk order   d_delta_pk NULL: the deltas are not ordered; d_upd_pk NULL: nor the updates (they need
+ *                  d_upd).  pk_lo / pk_hi bound every pk; delta_cap / upd_cap are the lists' capacities;
+ *                  the records' keys are read from d_delta_key / d_upd_key when given. */
+typedef struct kd_step {
+    const kd_side* base;
+    const kd_side* target;
+    const uint32_t* base_order;
+    const uint32_t* target_order;
+    uint32_t flags;
+    uint32_t reserved;
+    uint32_t* d_delta;
+    uint32_t* d_upd;
+    uint64_t* d_delta_key;
+    uint64_t* d_upd_key;
+    uint64_t* d_counts;
+    uint32_t* d_err;
+    const kd_blobs* old_blobs;
+    const kd_blobs* new_blobs;
+    const uint32_t* d_pairs;
+    uint64_t upd_cap;
+    const kd_legend_maps* maps;
+    uint64_t* d_masks;
+    uint8_t* d_status;
+    int64_t pk_lo;
+    int64_t pk_hi;
+    uint64_t delta_cap;
+    int64_t* d_delta_pk;
+    uint32_t* d_delta_perm;
+    int64_t* d_upd_pk;
+    uint32_t* d_upd_perm;
+} kd_step;
+/* Results are those of the separate calls in sequence, bit for bit.  The library owns the schedule: with
+ * the step_overlap option the placement (k_place2) and the pk order run on a stream of the context's own
+ * beside the field diff, which needs neither (a field diff given d_pairs reads the placed updates: then
+ * only the pk order runs beside it; KD_DIFF_UNORDERED, or nothing to overlap: one stream).  The context's
+ * stream waits for that work before the call returns, so whatever is queued on it next — kd_sync
+ * included — comes after the whole step.  Asynchronous. */
+int kd_diff2_step(kd_ctx* ctx, const kd_step* step);
 
 /* -------- device memory and copies (no GPU framework needed by the caller) -------- */
 #define KD_COPY_H2D 1u

@@ -105,6 +105,38 @@ class KdLegendMaps(ctypes.Structure):
     ]
 
 
+class KdStep(ctypes.Structure):
+    """kd_step (kd_diff2_step): the join's, the field diff's and the pk order's arguments"""
+    _fields_ = [
+        ("base", ctypes.POINTER(KdSide)),
+        ("target", ctypes.POINTER(KdSide)),
+        ("base_order", ctypes.c_void_p),
+        ("target_order", ctypes.c_void_p),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("d_delta", ctypes.c_void_p),
+        ("d_upd", ctypes.c_void_p),
+        ("d_delta_key", ctypes.c_void_p),
+        ("d_upd_key", ctypes.c_void_p),
+        ("d_counts", ctypes.c_void_p),
+        ("d_err", ctypes.c_void_p),
+        ("old_blobs", ctypes.POINTER(KdBlobs)),
+        ("new_blobs", ctypes.POINTER(KdBlobs)),
+        ("d_pairs", ctypes.c_void_p),
+        ("upd_cap", ctypes.c_uint64),
+        ("maps", ctypes.POINTER(KdLegendMaps)),
+        ("d_masks", ctypes.c_void_p),
+        ("d_status", ctypes.c_void_p),
+        ("pk_lo", ctypes.c_int64),
+        ("pk_hi", ctypes.c_int64),
+        ("delta_cap", ctypes.c_uint64),
+        ("d_delta_pk", ctypes.c_void_p),
+        ("d_delta_perm", ctypes.c_void_p),
+        ("d_upd_pk", ctypes.c_void_p),
+        ("d_upd_perm", ctypes.c_void_p),
+    ]
+
+
 class KdGeomCols(ctypes.Structure):
     _fields_ = [
         ("n_leg_old", ctypes.c_int32),
@@ -253,6 +285,7 @@ SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p]),
+    "kd_diff2_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(KdStep)]),
     "kd_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]),
     "kd_mfree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "kd_host_alloc": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]),

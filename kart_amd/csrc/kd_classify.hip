@@ -509,6 +509,113 @@ int kd_diff2_device_ex(kd_ctx* ctx, const kd_side* base, const kd_side* target, 
     return diff2_device(ctx, base, target, flags, d_delta, d_upd, d_counts, d_err, oa, ob, d_delta_key, d_upd_key);
 }
 
+// The whole step behind one call, so that the library sees the dependencies between its parts:
+//   k_partition2 -> k_join2 -> k_gscan2 -> k_place2 -> k_fielddiff -> pk order (deltas) -> pk order (updates)
+// is today's order on one stream, but the field diff of update-order arenas reads only the blobs and
+// the update count (k_gscan2's), and the placement and the pk order write only the record lists, the
+// key lists and the pk outputs.  With the step_overlap option the step forks after k_gscan2 (after
+// k_place2 when the field diff reads the pairs it writes): the tail runs on the context's side stream
+// beside the field diff, and the calling stream waits for it before the call returns.
+int kd_diff2_step(kd_ctx* ctx, const kd_step* s) {
+    KD_CHECK(ctx && s, "kd_diff2_step: NULL");
+    int rc;
+    if ((rc = check_side(s->base, "base")) || (rc = check_side(s->target, "target"))) return rc;
+    KD_CHECK(s->base->mem == KD_MEM_DEVICE && s->target->mem == KD_MEM_DEVICE, "kd_diff2_step: sides must be device memory");
+    KD_CHECK(s->d_delta && s->d_counts && s->d_err, "kd_diff2_step: NULL output");
+    KD_CHECK(!s->base_order == !s->target_order, "kd_diff2_step: both orders or neither");
+    KD_CHECK(!s->d_upd_key || (s->d_upd && s->d_delta_key), "kd_diff2_step: update keys need the update list and delta keys");
+    const bool have_fd = s->old_blobs != nullptr;
+    KD_CHECK(!have_fd || (s->new_blobs && s->maps && s->d_masks && s->d_status), "kd_diff2_step: field diff: NULL argument");
+    const bool have_dpk = s->d_delta_pk != nullptr, have_upk = s->d_upd_pk != nullptr;
+    KD_CHECK(!have_dpk || s->d_delta_perm, "kd_diff2_step: d_delta_pk without d_delta_perm");
+    KD_CHECK(!have_upk || (s->d_upd_perm && s->d_upd), "kd_diff2_step: d_upd_pk needs d_upd_perm and the update list");
+    KD_HIP(hipSetDevice(ctx->device));
+    void* dz = nullptr;
+    if ((rc = device_zeros(ctx, &dz))) return rc;  // (first use fills it on this stream: before any fork)
+    const u32* oa = s->base_order ? (s->base->n ? s->base_order : (const u32*)dz) : nullptr;
+    const u32* ob = s->target_order ? (s->target->n ? s->target_order : (const u32*)dz) : nullptr;
+    Diff2Place pl;
+    if ((rc = diff2_front(ctx, s->base, s->target, s->flags, s->d_delta, s->d_upd, s->d_counts, s->d_err, oa, ob,
+                          s->d_delta_key, s->d_upd_key, &pl)))
+        return rc;
+    const int ov = ctx->opt.step_overlap;
+    auto field_diff = [&]() -> int {
+        return have_fd ? kd_fielddiff(ctx, s->old_blobs, s->new_blobs, s->d_pairs, s->upd_cap, s->d_counts + 1,
+                                      KD_MEM_DEVICE, s->maps, s->d_masks, s->d_status, KD_MEM_DEVICE)
+                       : KD_OK;
+    };
+    auto pk_orders = [&](bool lds_free) -> int {
+        int r = KD_OK;
+        if (have_dpk)
+            r = delta_pk_order(ctx, s->base, s->target, s->d_delta, s->d_delta_key, s->delta_cap, s->d_counts + 3,
+                               s->pk_lo, s->pk_hi, s->d_delta_pk, s->d_delta_perm, lds_free);
+        if (!r && have_upk)
+            r = delta_pk_order(ctx, s->base, s->target, s->d_upd, s->d_upd_key, s->upd_cap, s->d_counts + 1, s->pk_lo,
+                               s->pk_hi, s->d_upd_pk, s->d_upd_perm, lds_free);
+        return r;
+    };
+    // A field diff given pairs reads d_upd: the placement then stays in front of it and only the pk
+    // order can go aside.  Nothing aside without a field diff to run beside, without a placement
+    // (KD_DIFF_UNORDERED, two empty sides), or with nothing to put there.
+    const bool place_aside = !(have_fd && s->d_pairs);
+    // (and not below step_overlap_min entries: a short field diff hides less than the two
+    // cross-stream waits cost — C2 measured 0.243 -> 0.247 ms, kd_internal.h)
+    const bool overlap = ov > 0 && have_fd && pl.needed && (place_aside || have_dpk || have_upk) &&
+                         s->base->n + s->target->n >= ctx->opt.step_overlap_min;
+    const int wave = ctx->opt.pkm_wave;
+    if (!overlap) {
+        if ((rc = diff2_place(ctx, pl)) || (rc = field_diff())) return rc;
+        return pk_orders(wave > 0);
+    }
+    if (!ctx->side_stream) {
+        KD_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+        KD_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        KD_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    }
+    // ctx->stream is the context's own or the one kd_set_stream installed: fork and join are events
+    // between it and the side stream, whichever it is
+    const hipStream_t main = ctx->stream, side = ctx->side_stream;
+    if (!place_aside && (rc = diff2_place(ctx, pl))) return rc;
+    KD_HIP(hipEventRecord(ctx->ev_fork, main));
+    // ---- forked from here: every path below runs through the join at the end ----
+    auto side_work = [&]() -> int {
+        // (ensure() inside also waits for `main` before it frees a buffer: kd::StreamScope)
+        StreamScope scope(ctx, side);
+        KD_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
+        int r = place_aside ? diff2_place(ctx, pl) : KD_OK;
+        // The pk masks: both calls run here in order on the side stream, like two calls on one
+        // stream, so pkm_cur / pkm_zero_* describe the buffers as the kernels find them; the call
+        // before this step was ordered before the fork, and any later call comes after the join.
+        return r ? r : pk_orders(wave != 0);
+    };
+    int rc_fd, rc_side = KD_OK;
+    if (ov == 2) {
+        rc_side = side_work();
+        rc_fd = field_diff();
+    } else {
+        rc_fd = field_diff();
+        if (!rc_fd) rc_side = side_work();
+    }
+    // The join back, on error paths too: `main` waits for everything queued on the side stream, so
+    //  - any later call on the context's stream is ordered after the side work — the next step's
+    //    k_partition2 zeroes c2.gsum and its join overwrites c2.sdel / c2.skd / c2.tcnt, which this
+    //    step's k_place2 reads, and the next pk order marks the masks this one's scan cleared;
+    //  - ensure()'s synchronise-before-realloc and kd_sync, which wait for the context's stream,
+    //    still cover all of the step.
+    // If an event call fails, the host waits for the side stream instead: nothing is left running
+    // there when this returns.
+    hipError_t e = hipEventRecord(ctx->ev_join, side);
+    if (e == hipSuccess) e = hipStreamWaitEvent(main, ctx->ev_join, 0);
+    if (e != hipSuccess) {
+        const hipError_t e2 = hipStreamSynchronize(side);
+        if (!rc_fd && !rc_side) {
+            set_error("kd_diff2_step: join: %s", hipGetErrorString(e2 != hipSuccess ? e2 : e));
+            return KD_EHIP;
+        }
+    }
+    return rc_fd ? rc_fd : rc_side;
+}
+
 int kd_diff2(kd_ctx* ctx, const kd_side* base, const kd_side* target, uint32_t flags, kd_diff_result** out) {
     KD_CHECK(ctx && out, "kd_diff2: NULL");
     int rc;

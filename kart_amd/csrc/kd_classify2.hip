@@ -1912,6 +1912,14 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
 
 int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd,
                  u64* d_counts, u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey) {
+    Diff2Place pl;
+    int rc = diff2_front(ctx, A, B, flags, d_delta, d_upd, d_counts, d_err, ordA, ordB, d_dkey, d_ukey, &pl);
+    return rc ? rc : diff2_place(ctx, pl);
+}
+
+int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd, u64* d_counts,
+                u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey, Diff2Place* pl) {
+    *pl = Diff2Place{};
     const bool unord = (flags & KD_DIFF_UNORDERED) != 0;
     const u64 nA = A->n, nB = B->n, total = nA + nB;
     KD_CHECK(nA < 0xFFFFFFFFull && nB < 0xFFFFFFFFull, "diff2: side too large for uint32 indices");
@@ -2005,10 +2013,20 @@ int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32
                            (u64*)gpre, d_counts, 0);
     });
     if (rc) return rc;
+    pl->needed = true;
+    pl->ntiles = ntiles;
+    pl->sdel = sdel; pl->tcnt = tcnt; pl->gpre = gpre; pl->skd = skd;
+    pl->d_delta = d_delta; pl->d_upd = d_upd;
+    pl->d_dkey = d_dkey; pl->d_ukey = d_upd ? d_ukey : nullptr;
+    return KD_OK;
+}
+
+int diff2_place(kd_ctx* ctx, const Diff2Place& pl) {
+    if (!pl.needed) return KD_OK;
     return launch(ctx, "k_place2", [&] {
-        hipLaunchKernelGGL((k_place2<KD_PLACE_NT>), dim3((unsigned)ntiles), dim3(KD_PLACE_NT), 0, ctx->stream,
-                           (const uint2*)sdel, (const u32*)tcnt, (const u64*)gpre, (int)C2_STAGE, (uint2*)d_delta,
-                           (uint2*)d_upd, (const u64*)skd, d_dkey, d_upd ? d_ukey : nullptr);
+        hipLaunchKernelGGL((k_place2<KD_PLACE_NT>), dim3((unsigned)pl.ntiles), dim3(KD_PLACE_NT), 0, ctx->stream,
+                           (const uint2*)pl.sdel, (const u32*)pl.tcnt, (const u64*)pl.gpre, (int)C2_STAGE,
+                           (uint2*)pl.d_delta, (uint2*)pl.d_upd, (const u64*)pl.skd, pl.d_dkey, pl.d_ukey);
     });
 }
 

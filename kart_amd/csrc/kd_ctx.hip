@@ -29,6 +29,9 @@ int ensure(kd_ctx* ctx, const char* slot, size_t bytes, void** out) {
     if (b.bytes < bytes) {
         if (b.p) {
             hipError_t e = hipStreamSynchronize(ctx->stream);
+            // (inside kd_diff2_step's side work ctx->stream is the side stream: the stream the step
+            // was called on may still run the field diff, so the old buffer waits for it too)
+            if (e == hipSuccess && ctx->step_main) e = hipStreamSynchronize(ctx->step_main);
             if (e != hipSuccess) { set_error("sync before realloc: %s", hipGetErrorString(e)); return KD_EHIP; }
             if (!b.slab) KD_HIP(hipFree(b.p));  // (a slab piece is abandoned)
             b.p = nullptr;
@@ -321,6 +324,9 @@ const OptDef OPTS[] = {
     {"fd_walk", "KD_FD_WALK", nullptr, &kd_opts::fd_walk, nullptr},
     {"pkm_max_blocks", "KD_PKM_MAX_BLOCKS", nullptr, nullptr, &kd_opts::pkm_max_blocks},
     {"trace_host", "KD_TRACE_HOST", nullptr, &kd_opts::trace_host, nullptr},
+    {"step_overlap", "KD_STEP_OVERLAP", nullptr, &kd_opts::step_overlap, nullptr},
+    {"step_overlap_min", "KD_STEP_OVERLAP_MIN", nullptr, nullptr, &kd_opts::step_overlap_min},
+    {"pkm_wave", "KD_PKM_WAVE", nullptr, &kd_opts::pkm_wave, nullptr},
 };
 void opt_set(kd_opts& o, const OptDef& d, int64_t v) {
     if (d.i32) o.*(d.i32) = (int)v;
@@ -439,6 +445,14 @@ int kd_fini(kd_ctx* ctx) {
     prof_flush(ctx);
     comm_release(ctx);
     gather_release(ctx);
+    // kd_diff2_step's side stream: every step joined it back into the stream it was called on (a
+    // caller's stream, if kd_set_stream has changed since, is not the one synchronised above)
+    if (ctx->side_stream) {
+        (void)hipStreamSynchronize(ctx->side_stream);
+        (void)hipStreamDestroy(ctx->side_stream);
+    }
+    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     for (auto& kv : ctx->bufs)
         if (kv.second.p && !kv.second.slab) (void)hipFree(kv.second.p);
     if (ctx->slab) (void)hipFree(ctx->slab);

@@ -76,6 +76,18 @@ struct kd_opts {
     int fd_walk = -1;                // KD_FD_WALK: -1 / 0 off, 1 the walked k_fdwalk (A/B)
     uint64_t pkm_max_blocks = 1ull << 26;  // KD_PKM_MAX_BLOCKS: largest pk range (64-pk blocks) of the bitmap pk order
     int trace_host = 0;              // KD_TRACE_HOST: 1 = stream-synced wall-clock marks to stderr
+    // KD_STEP_OVERLAP: kd_diff2_step's schedule — 0 everything on the context's stream; 1 / 2 the
+    // placement and the pk order on the side stream beside the field diff, which is queued first (1)
+    // or after them (2)
+    int step_overlap = 1;
+    // KD_STEP_OVERLAP_MIN: the side stream is used from this many entries of both sides together.
+    // Measured (profiles/step_overlap/bench_ab.json): C3's 200M-entry step gains 0.11 ms of 2.92; C2's
+    // 20M-entry step, whose field diff runs 40 us, loses 0.004 ms of 0.243 to the two cross-stream
+    // waits.  2^26 lies between the two.
+    uint64_t step_overlap_min = 1ull << 26;
+    // KD_PKM_WAVE: the bitmap pk order's scans in their LDS-free one-wave-per-chunk form: -1 on
+    // kd_diff2_step's side stream only, 0 never, 1 always
+    int pkm_wave = -1;
 };
 
 struct kd_ctx {
@@ -84,6 +96,13 @@ struct kd_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::map<std::string, kd::DevBuf> bufs;
+    // kd_diff2_step's side stream (created on first use, released by kd_fini) and its fork / join
+    // events.  While the step queues the side work, `stream` IS the side stream (kd::StreamScope:
+    // every launch, copy and profiling event of the library goes to ctx->stream) and step_main is the
+    // stream the step was called on; nullptr outside that window.
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipStream_t step_main = nullptr;
     // profiling
     bool prof = false;
     std::string prof_only;  // ",name,name," selection (empty = every kernel)
@@ -150,6 +169,24 @@ int device_zeros(kd_ctx* ctx, void** out);
 // context's device (>= 1), from the occupancy calculator once per context
 int occupancy(kd_ctx* ctx, const void* kernel, int block, size_t lds);
 
+// ctx->stream pointed at another stream for a scope (kd_diff2_step's side work): launch(),
+// prof_begin / prof_end, ensure() and every entry point's body follow ctx->stream, so the events of
+// a kernel are recorded on the stream it was launched on
+struct StreamScope {
+    kd_ctx* ctx;
+    hipStream_t saved;
+    StreamScope(kd_ctx* c, hipStream_t s) : ctx(c), saved(c->stream) {
+        c->step_main = saved;
+        c->stream = s;
+    }
+    ~StreamScope() {
+        ctx->stream = saved;
+        ctx->step_main = nullptr;
+    }
+    StreamScope(const StreamScope&) = delete;
+    StreamScope& operator=(const StreamScope&) = delete;
+};
+
 // profiling wrappers around a launch on ctx->stream
 void prof_begin(kd_ctx* ctx, const char* name, hipEvent_t* a);
 void prof_end(kd_ctx* ctx, const char* name, hipEvent_t a);
@@ -198,6 +235,24 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
 int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta,
                  u32* d_upd, u64* d_counts, u32* d_err, const u32* ordA = nullptr, const u32* ordB = nullptr,
                  u64* d_dkey = nullptr, u64* d_ukey = nullptr);
+// diff2_device in two parts (kd_diff2_step queues them on different streams): the front runs
+// k_partition2, k_join2 and k_gscan2 — the counts are final after it — and fills `pl` with what the
+// placement needs; diff2_place launches k_place2 on ctx->stream (nothing to do when !pl.needed:
+// KD_DIFF_UNORDERED, or two empty sides)
+struct Diff2Place {
+    bool needed = false;
+    u64 ntiles = 0;
+    const void *sdel = nullptr, *tcnt = nullptr, *gpre = nullptr, *skd = nullptr;
+    u32 *d_delta = nullptr, *d_upd = nullptr;
+    u64 *d_dkey = nullptr, *d_ukey = nullptr;
+};
+int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd, u64* d_counts,
+                u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey, Diff2Place* pl);
+int diff2_place(kd_ctx* ctx, const Diff2Place& pl);
+// kd_delta_pk_order's body; lds_free: the scans in their one-wave-per-chunk form (no LDS, so they
+// become resident beside a field diff that fills every CU's LDS)
+int delta_pk_order(kd_ctx* ctx, const kd_side* base, const kd_side* target, const u32* d_delta, const u64* d_keys,
+                   u64 cap, const u64* d_n, i64 pk_lo, i64 pk_hi, i64* d_pk, u32* d_perm, bool lds_free);
 #ifndef KD_C2_NT
 #define KD_C2_NT 256
 #endif

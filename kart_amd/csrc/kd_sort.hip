@@ -495,6 +495,11 @@ __global__ __launch_bounds__(RS_HIST_NT) void k_dpk_keys(const uint2* __restrict
 #define KD_PKM_IPT 16  // masks per scan thread (r4pk, C3: 2 / 4 / 8 / 16 -> scan 0.111 / 0.074 / 0.052 / 0.038 ms)
 #endif
 constexpr int PKM_NT = 256, PKM_IPT = KD_PKM_IPT, PKM_CH = PKM_NT * PKM_IPT;
+// The LDS-free scans (kd_diff2_step's side stream, beside a field diff whose resident grid holds
+// every CU's LDS for its whole run — a block that asks for any LDS would wait for it to finish): a
+// chunk is what one wave scans with shuffles alone, PKM_CHW masks; the blocks still hold PKM_NT / 64
+// waves, each on its own chunk, so thread t of block b reads the same masks in both forms.
+constexpr int PKM_CHW = 64 * PKM_IPT;
 
 __global__ __launch_bounds__(PKM_NT) void k_pkm_mark(const uint2* __restrict__ rec, u64 ncap, const u64* __restrict__ dn,
                                                      const u64* __restrict__ kA, const u64* __restrict__ kB,
@@ -538,9 +543,10 @@ __global__ __launch_bounds__(PKM_NT) void k_pkm_mark(const uint2* __restrict__ r
 // (masks and local prefixes moved 16 B per access; each thread's PKM_IPT masks are one 128-B line)
 static_assert(PKM_IPT % 4 == 0, "k_pkm_scan: 16-B loads and stores");
 // (zero: the other mask buffer, cleared here for the next call — no fill launch per call)
+// WAVE: one chunk of PKM_CHW masks per wave (no LDS, no barrier), nch of them
+template <bool WAVE>
 __global__ __launch_bounds__(PKM_NT) void k_pkm_scan(const u64* __restrict__ masks, u64 nb, u32* __restrict__ local,
-                                                     u32* __restrict__ chunk_tot, u64* __restrict__ zero) {
-    __shared__ u32 s_wave[PKM_NT / 64];
+                                                     u32* __restrict__ chunk_tot, u64* __restrict__ zero, u64 nch) {
     const int tid = threadIdx.x;
     const u64 c0 = (u64)blockIdx.x * PKM_CH + (u64)tid * PKM_IPT;
     u32 cnt[PKM_IPT], sum = 0;
@@ -564,8 +570,21 @@ __global__ __launch_bounds__(PKM_NT) void k_pkm_scan(const u64* __restrict__ mas
     }
 #pragma unroll
     for (int j = 0; j < PKM_IPT; j++) sum += cnt[j];
-    u32 tot;
-    u32 ex = block_scan_u32<PKM_NT>(sum, s_wave, &tot);
+    u32 tot, ex;
+    if constexpr (WAVE) {
+        const int lane = tid & 63;
+        u32 x = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const u32 y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        tot = __shfl(x, 63, 64);
+        ex = x - sum;
+    } else {
+        __shared__ u32 s_wave[PKM_NT / 64];
+        ex = block_scan_u32<PKM_NT>(sum, s_wave, &tot);
+    }
     if (c0 + PKM_IPT <= nb) {
         u32x4* l4 = (u32x4*)(local + c0);
 #pragma unroll
@@ -584,7 +603,12 @@ __global__ __launch_bounds__(PKM_NT) void k_pkm_scan(const u64* __restrict__ mas
             ex += cnt[j];
         }
     }
-    if (tid == 0) chunk_tot[blockIdx.x] = tot;
+    if constexpr (WAVE) {
+        const u64 ch = (u64)blockIdx.x * (PKM_NT / 64) + (u64)(tid >> 6);  // (the last block's waves may lie past nch)
+        if ((tid & 63) == 0 && ch < nch) chunk_tot[ch] = tot;
+    } else {
+        if (tid == 0) chunk_tot[blockIdx.x] = tot;
+    }
 }
 
 // one block: exclusive scan of the chunk totals (a kernel of its own: the launch boundary orders it
@@ -615,6 +639,37 @@ __global__ __launch_bounds__(1024) void k_pkm_cscan(const u32* __restrict__ chun
     }
 }
 
+// the LDS-free form: one wave, PKC_WPT chunk totals per lane and pass, shuffles only
+constexpr int PKC_WPT = 32;
+__global__ __launch_bounds__(64) void k_pkm_cscan_w(const u32* __restrict__ chunk_tot, u32 nch, u32* __restrict__ chunk_pre) {
+    const int lane = threadIdx.x;
+    u32 carry = 0;
+    for (u32 base = 0; base < nch; base += 64 * PKC_WPT) {  // (wave-uniform)
+        const u32 k0 = base + (u32)lane * PKC_WPT;
+        u32 v[PKC_WPT], sum = 0;
+#pragma unroll
+        for (int j = 0; j < PKC_WPT; j++) {
+            v[j] = k0 + j < nch ? chunk_tot[k0 + j] : 0u;
+            sum += v[j];
+        }
+        u32 x = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const u32 y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        u32 e = carry + x - sum;
+#pragma unroll
+        for (int j = 0; j < PKC_WPT; j++) {
+            if (k0 + j < nch) chunk_pre[k0 + j] = e;
+            e += v[j];
+        }
+        carry += __shfl(x, 63, 64);
+    }
+}
+
+// CH: the scan's chunk (PKM_CH, or PKM_CHW after the LDS-free scans)
+template <int CH>
 __global__ __launch_bounds__(PKM_NT) void k_pkm_place(const i64* __restrict__ pks, const u64* __restrict__ rkey, u64 ncap,
                                                       const u64* __restrict__ dn, i64 lo_block, u64 nb,
                                                       const u64* __restrict__ masks, const u32* __restrict__ local,
@@ -626,7 +681,7 @@ __global__ __launch_bounds__(PKM_NT) void k_pkm_place(const i64* __restrict__ pk
         const u64 b = (u64)((pk >> 6) - lo_block);
         if (b >= nb) continue;
         const u64 below = masks[b] & ((1ull << (pk & 63)) - 1);
-        const u32 pos = chunk_pre[b / PKM_CH] + local[b] + (u32)__popcll(below);
+        const u32 pos = chunk_pre[b / CH] + local[b] + (u32)__popcll(below);
         out_pk[pos] = pk;
         out_perm[pos] = (u32)r;
     }
@@ -1168,6 +1223,17 @@ extern "C" int kd_sort_segmented_into(kd_ctx* ctx, const uint64_t* d_key_in, uin
 extern "C" int kd_delta_pk_order(kd_ctx* ctx, const kd_side* base, const kd_side* target, const uint32_t* d_delta,
                                  const uint64_t* d_keys, uint64_t cap, const uint64_t* d_n, int64_t pk_lo, int64_t pk_hi,
                                  int64_t* d_pk, uint32_t* d_perm) {
+    KD_CHECK(ctx, "kd_delta_pk_order: NULL");
+    return delta_pk_order(ctx, base, target, d_delta, d_keys, cap, d_n, pk_lo, pk_hi, d_pk, d_perm, false);
+}
+
+// (queued on ctx->stream, like everything it calls: kd_diff2_step runs it on its side stream through
+// a kd::StreamScope.  The mask bookkeeping in pkm_cur / pkm_zero_* is host state in call order and the
+// kernels it describes run in stream order: valid as long as consecutive calls are ordered on the
+// device, which two calls on one stream are and which the step's fork and join events keep across
+// streams.)
+int kd::delta_pk_order(kd_ctx* ctx, const kd_side* base, const kd_side* target, const u32* d_delta, const u64* d_keys,
+                       u64 cap, const u64* d_n, i64 pk_lo, i64 pk_hi, i64* d_pk, u32* d_perm, bool lds_free) {
     KD_CHECK(ctx && base && target && d_n && d_pk && d_perm && (cap == 0 || d_delta || d_keys), "kd_delta_pk_order: NULL");
     KD_CHECK(base->key_mode == KD_KEY_INT && target->key_mode == KD_KEY_INT, "kd_delta_pk_order: KD_KEY_INT sides only");
     KD_CHECK(base->mem == KD_MEM_DEVICE && target->mem == KD_MEM_DEVICE, "kd_delta_pk_order: sides must be device memory");
@@ -1184,9 +1250,10 @@ extern "C" int kd_delta_pk_order(kd_ctx* ctx, const kd_side* base, const kd_side
     const i64 lo_block = pk_lo >> 6, hi_block = pk_hi >> 6;
     const u64 nb = (u64)hi_block - (u64)lo_block + 1;
     const u64 pkm_max = ctx->opt.pkm_max_blocks;  // (tests force the radix path with 0)
-    if (nb <= pkm_max && nb / PKM_CH < 0xFFFFFFFFull) {
+    if (nb <= pkm_max && nb / PKM_CHW < 0xFFFFFFFFull) {
         void *mbuf[2], *local, *ctot, *cpre, *tpk;
-        const u64 nch = (nb + PKM_CH - 1) / PKM_CH;
+        const u64 chunk = lds_free ? PKM_CHW : PKM_CH;
+        const u64 nch = (nb + chunk - 1) / chunk;
         if ((rc = ensure(ctx, "pkm.masks0", nb * 8, &mbuf[0]))) return rc;
         if ((rc = ensure(ctx, "pkm.masks1", nb * 8, &mbuf[1]))) return rc;
         const int cur = ctx->pkm_cur & 1;
@@ -1210,20 +1277,31 @@ extern "C" int kd_delta_pk_order(kd_ctx* ctx, const kd_side* base, const kd_side
         });
         if (rc) return rc;
         rc = launch(ctx, "k_pkm_scan", [&] {
-            hipLaunchKernelGGL(k_pkm_scan, dim3((unsigned)nch), dim3(PKM_NT), 0, ctx->stream, (const u64*)masks, nb,
-                               (u32*)local, (u32*)ctot, (u64*)other);
+            if (lds_free)
+                hipLaunchKernelGGL(k_pkm_scan<true>, dim3((unsigned)((nch + PKM_NT / 64 - 1) / (PKM_NT / 64))), dim3(PKM_NT),
+                                   0, ctx->stream, (const u64*)masks, nb, (u32*)local, (u32*)ctot, (u64*)other, nch);
+            else
+                hipLaunchKernelGGL(k_pkm_scan<false>, dim3((unsigned)nch), dim3(PKM_NT), 0, ctx->stream, (const u64*)masks,
+                                   nb, (u32*)local, (u32*)ctot, (u64*)other, nch);
         });
         if (rc) return rc;
         ctx->pkm_zero_ptr[cur ^ 1] = other;  // zero for [0, nb) once the scan has run (stream order)
         ctx->pkm_zero_nb[cur ^ 1] = nb;
         ctx->pkm_cur = cur ^ 1;
         rc = launch(ctx, "k_pkm_cscan", [&] {
-            hipLaunchKernelGGL(k_pkm_cscan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)ctot, (u32)nch, (u32*)cpre);
+            if (lds_free)
+                hipLaunchKernelGGL(k_pkm_cscan_w, dim3(1), dim3(64), 0, ctx->stream, (const u32*)ctot, (u32)nch, (u32*)cpre);
+            else
+                hipLaunchKernelGGL(k_pkm_cscan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)ctot, (u32)nch, (u32*)cpre);
         });
         if (rc) return rc;
         return launch(ctx, "k_pkm_place", [&] {
-            hipLaunchKernelGGL(k_pkm_place, dim3(g1), dim3(PKM_NT), 0, ctx->stream, (const i64*)tpk, d_keys, cap, d_n,
-                               lo_block, nb, (const u64*)masks, (const u32*)local, (const u32*)cpre, d_pk, d_perm);
+            if (lds_free)
+                hipLaunchKernelGGL(k_pkm_place<PKM_CHW>, dim3(g1), dim3(PKM_NT), 0, ctx->stream, (const i64*)tpk, d_keys, cap,
+                                   d_n, lo_block, nb, (const u64*)masks, (const u32*)local, (const u32*)cpre, d_pk, d_perm);
+            else
+                hipLaunchKernelGGL(k_pkm_place<PKM_CH>, dim3(g1), dim3(PKM_NT), 0, ctx->stream, (const i64*)tpk, d_keys, cap,
+                                   d_n, lo_block, nb, (const u64*)masks, (const u32*)local, (const u32*)cpre, d_pk, d_perm);
         });
     }
     SortPlan plan = pk_plan(pk_lo, pk_hi);

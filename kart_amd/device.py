@@ -179,8 +179,8 @@ class DevBlobs:
 
 
 class DiffPipeline:
-    """classify2 + fielddiff (+ the deltas in pk order) over device-resident sides (one GPU), back to
-    back on one stream.
+    """classify2 + fielddiff (+ the deltas in pk order) over device-resident sides (one GPU), one
+    kd_diff2_step call per step.
 
     The sides are as the tree walk lists them: for int pks that is ascending key order already
     (kart_amd/walkkey.py), so a step is the join on the walk-order arrays, the field diff of its
@@ -243,6 +243,7 @@ class DiffPipeline:
         self._ob, self._nb = self.OB.kd_blobs(), self.NB.kd_blobs()
         self._km = maps.kd_maps()
         self._perm_sides = None
+        self._steps = {}  # kd_diff2_step argument blocks by form (_step_args)
         # pk order of the deltas and updates (KD_KEY_INT): the passes sized by the pk range
         self.pk_order = bool(pk_order) and base.key_mode == N.KD_KEY_INT and gather is None
         if self.pk_order:
@@ -301,6 +302,7 @@ class DiffPipeline:
                 b = arena.kd_blobs()
             blobs.append(b)
         self._ob_u, self._nb_u = blobs
+        self._steps = {}
 
     def reserve_gather(self, max_deltas_per_rank):
         """size the gathered-record buffer for at most this many deltas on any rank"""
@@ -339,6 +341,35 @@ class DiffPipeline:
     def _diff(self, perm):
         L, ctx = self.eng.L, self.eng.ctx
         keys = self.pk_order and self.flags == 0
+        if self.gather is None:
+            # one call: the library owns the schedule of the step's kernels (kd_diff2_step)
+            N.check(L.kd_diff2_step(ctx, ctypes.byref(self._step_args(perm, keys))), "kd_diff2_step")
+            return
+        # the join, rebase and counts' all-gather; the field diff is queued before anything waits
+        # for the counts, and the records' all-gather (communication stream) overlaps it
+        N.check(L.kd_diff2_gather_begin(ctx, ctypes.byref(self._sa), ctypes.byref(self._sb), self.gather[0],
+                                        self.gather[1], self.flags, self.delta.ptr, self.upd.ptr, self.counts.ptr,
+                                        self.counts.ptr + 32, self.all_counts.ptr), "kd_diff2_gather_begin")
+        if self._ob_u is not None:  # update-order arenas: update i's blobs at index i, no pairs
+            N.check(L.kd_fielddiff(ctx, ctypes.byref(self._ob_u), ctypes.byref(self._nb_u), None, self.cap_upd,
+                                   ctypes.cast(self.counts.ptr + 8, N.c_u64p), N.KD_MEM_DEVICE,
+                                   ctypes.byref(self._km), self.masks.ptr, self.status.ptr, N.KD_MEM_DEVICE),
+                    "kd_fielddiff")
+        else:
+            N.check(L.kd_fielddiff(ctx, ctypes.byref(self._ob), ctypes.byref(self._nb), self.upd.ptr, self.cap_upd,
+                                   ctypes.cast(self.counts.ptr + 8, N.c_u64p), N.KD_MEM_DEVICE,
+                                   ctypes.byref(self._km), self.masks.ptr, self.status.ptr, N.KD_MEM_DEVICE),
+                    "kd_fielddiff")
+        N.check(L.kd_diff2_gather_end(ctx, self.delta.ptr, self.all_delta.ptr, self.all_cap,
+                                      self.h_counts.ctypes.data), "kd_diff2_gather_end")
+
+    def _step_args(self, perm, keys):
+        """kd_diff2_step's arguments for this pipeline (built once per form: the buffers never move)"""
+        form = (bool(perm), bool(keys), self._ob_u is not None)
+        st = self._steps.get(form)
+        if st is not None:
+            return st
+        st = N.KdStep()
         if perm:  # sorted keys; OIDs and filenames read through the sort orders from the walk-order rows
             if self._perm_sides is None:
                 self._perm_sides = []
@@ -348,42 +379,29 @@ class DiffPipeline:
                     if w.name is not None:
                         k.name, k.name_off = w.name.ptr, w.name_off.ptr
                     self._perm_sides.append(k)
-            N.check(L.kd_diff2_device_ex(ctx, ctypes.byref(self._perm_sides[0]), ctypes.byref(self._perm_sides[1]),
-                                         self.walk[0][1].ptr, self.walk[1][1].ptr, self.flags, self.delta.ptr,
-                                         self.upd.ptr, self.dkey.ptr if keys else None, self.ukey.ptr if keys else None,
-                                         self.counts.ptr, self.counts.ptr + 32), "kd_diff2_device_ex")
-        elif self.gather is None:
-            N.check(L.kd_diff2_device_ex(ctx, ctypes.byref(self._sa), ctypes.byref(self._sb), None, None, self.flags,
-                                         self.delta.ptr, self.upd.ptr, self.dkey.ptr if keys else None,
-                                         self.ukey.ptr if keys else None, self.counts.ptr, self.counts.ptr + 32),
-                    "kd_diff2_device_ex")
+            st.base, st.target = ctypes.pointer(self._perm_sides[0]), ctypes.pointer(self._perm_sides[1])
+            st.base_order, st.target_order = self.walk[0][1].ptr, self.walk[1][1].ptr
         else:
-            # the join, rebase and counts' all-gather; the field diff is queued before anything waits
-            # for the counts, and the records' all-gather (communication stream) overlaps it
-            N.check(L.kd_diff2_gather_begin(ctx, ctypes.byref(self._sa), ctypes.byref(self._sb), self.gather[0],
-                                            self.gather[1], self.flags, self.delta.ptr, self.upd.ptr, self.counts.ptr,
-                                            self.counts.ptr + 32, self.all_counts.ptr), "kd_diff2_gather_begin")
+            st.base, st.target = ctypes.pointer(self._sa), ctypes.pointer(self._sb)
+        st.flags = self.flags
+        st.d_delta, st.d_upd = self.delta.ptr, self.upd.ptr
+        st.d_counts, st.d_err = self.counts.ptr, self.counts.ptr + 32
         if self._ob_u is not None:  # update-order arenas: update i's blobs at index i, no pairs
-            N.check(L.kd_fielddiff(ctx, ctypes.byref(self._ob_u), ctypes.byref(self._nb_u), None, self.cap_upd,
-                                   ctypes.cast(self.counts.ptr + 8, N.c_u64p), N.KD_MEM_DEVICE,
-                                   ctypes.byref(self._km), self.masks.ptr, self.status.ptr, N.KD_MEM_DEVICE),
-                    "kd_fielddiff")
+            st.old_blobs, st.new_blobs = ctypes.pointer(self._ob_u), ctypes.pointer(self._nb_u)
         else:
-            N.check(L.kd_fielddiff(ctx, ctypes.byref(self._ob), ctypes.byref(self._nb), self.upd.ptr, self.cap_upd,
-                               ctypes.cast(self.counts.ptr + 8, N.c_u64p), N.KD_MEM_DEVICE,
-                                   ctypes.byref(self._km), self.masks.ptr, self.status.ptr, N.KD_MEM_DEVICE),
-                    "kd_fielddiff")
+            st.old_blobs, st.new_blobs = ctypes.pointer(self._ob), ctypes.pointer(self._nb)
+            st.d_pairs = self.upd.ptr
+        st.upd_cap = self.cap_upd
+        st.maps = ctypes.pointer(self._km)
+        st.d_masks, st.d_status = self.masks.ptr, self.status.ptr
         if keys:
-            lo, hi = self.pk_range
-            N.check(L.kd_delta_pk_order(ctx, ctypes.byref(self._sa), ctypes.byref(self._sb), self.delta.ptr,
-                                        self.dkey.ptr, self.cap, self.counts.ptr + 24, lo, hi, self.d_pk.ptr,
-                                        self.d_perm.ptr), "kd_delta_pk_order")
-            N.check(L.kd_delta_pk_order(ctx, ctypes.byref(self._sa), ctypes.byref(self._sb), self.upd.ptr,
-                                        self.ukey.ptr, max(self.cap_upd, 1), self.counts.ptr + 8, lo, hi, self.u_pk.ptr,
-                                        self.u_perm.ptr), "kd_delta_pk_order")
-        if self.gather is not None:
-            N.check(L.kd_diff2_gather_end(ctx, self.delta.ptr, self.all_delta.ptr, self.all_cap,
-                                          self.h_counts.ctypes.data), "kd_diff2_gather_end")
+            st.d_delta_key, st.d_upd_key = self.dkey.ptr, self.ukey.ptr
+            st.pk_lo, st.pk_hi = self.pk_range
+            st.delta_cap = self.cap
+            st.d_delta_pk, st.d_delta_perm = self.d_pk.ptr, self.d_perm.ptr
+            st.d_upd_pk, st.d_upd_perm = self.u_pk.ptr, self.u_perm.ptr
+        self._steps[form] = st
+        return st
 
     def results(self):
         """host copies (synchronous): counts dict, delta [n,2], upd [m,2], masks, status"""
