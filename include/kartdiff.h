@@ -148,6 +148,12 @@ int kd_set_stream(kd_ctx* ctx, void* hip_stream);
  *   j3_v           [KD_J3_V]           1: k_join3b (every tile range in one LDS-DMA batch); 0: k_join3
  *   j2_oidlds_min  [KD_J2_OIDLDS_MIN]  k_join2 stages OIDs in LDS from this many entries (2^26)
  *   j2r            [KD_J2R]            1: the persistent register-prefetched int-key join
+ *   j2_walk        [KD_J2_WALK]        the join tile's work out of LDS: 1 (default) guided split search (a verified
+ *                                      bracket around the proportional guess, the blind search when a wave's
+ *                                      bracket fails), a walk without per-item guards in full waves, and in
+ *                                      k_join2 the complete order check as straight-line reads issued with
+ *                                      the search's first; 0: the blind 4-ary search, guarded walk and looped
+ *                                      check.  Same results either way
  *   fd_stream      [KD_FD_STREAM]      -1 auto, 0 windowed, 1 streamed field diff (contiguous arenas)
  *   fd_walk        [KD_FD_WALK]        -1 / 0 off, 1 the walked field diff (A/B)
  *   pkm_max_blocks [KD_PKM_MAX_BLOCKS] largest pk range (64-pk blocks) kd_delta_pk_order places by bitmap

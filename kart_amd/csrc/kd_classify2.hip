@@ -169,6 +169,7 @@ struct Join2Args {
     u64* counts;         // [4] inserts, updates, deletes, deltas
     u32* err;
     u64 ntiles;
+    int walk;            // the j2_walk option
 };
 
 // A byte range of one input array, copied to LDS as 16-byte chunks of its 16-byte-aligned
@@ -268,25 +269,30 @@ __device__ __forceinline__ TileRanges tile_ranges(const Join2Args& g, const Tile
 
 enum : u32 { R_NONE = 0, R_DEL = 1, R_MATCH = 2, R_INS = 3 };
 
-// Merge path of one tile out of LDS, branch-free (selects instead of divergent branches: SALU
-// exec-mask traffic was the join's largest instruction stream).  4-ary search for the thread's
-// split — 3 independent probes per round, a fixed round count (5 for a 1024-item tile) — then a
-// walk over IPT items with the current and previous keys in registers (one LDS round trip per item;
-// the strictly-ascending check compares registers), then the OID compare of the matched pairs with
-// every LDS read issued before any compare.  Outcome per item:
-//   rec = kind << 25 | changed << 24 | jb << 12 | ia          (tile-local indices)
-template <int NT, int IPT>
-__device__ __forceinline__ void tile_walk(const u64* sA, const u64* sB, const TileGeo& q, u32 rec[IPT], bool& bad) {
-    using LD = Join2Lds<NT, IPT>;
-    const int tid = threadIdx.x, na = q.na, nb = q.nb;
-    const int nitems = na + nb;
-    const int nbx = nb + (q.has_la ? 1 : 0);  // B keys in LDS, including the lookahead
-    const int dd = tid * IPT < nitems ? tid * IPT : nitems;
-    const int cnt = (dd + IPT < nitems ? dd + IPT : nitems) - dd;
-    int lo = dd - nb > 0 ? dd - nb : 0, hi = dd < na ? dd : na;
-    // first i in [lo, hi] with i == hi || sA[i] > sB[dd-1-i]  (ties: A first)
+// timing probes only (results invalid; `make probe PFLAGS=-DKD_J2_PROBE=n`): a bit set compiles one
+// part of the tile's work out — 1 the split search (the proportional guess stands), 2 k_join2's
+// complete order check, 4 k_join2's OID compare from LDS, 8 the walk (no item: nothing compared or written)
+#ifndef KD_J2_PROBE
+#define KD_J2_PROBE 0
+#endif
+
+// the guided split search's bracket around the proportional guess g is [g - W, g + W - 1]: W = 8
+// leaves a width of 15, which two 4-ary rounds finish (W = 16 takes three and measured 5-16 us slower
+// at C3)
+constexpr int J2_GW = 8;
+// 4-ary rounds until a width of w is 0: the widest part a round leaves is its last, w - 3 * ceil(w / 4),
+// or one of the first three, ceil(w / 4) - 1
+constexpr int split_rounds_for(int w) {
+    return w <= 0 ? 0 : 1 + split_rounds_for(((w + 3) / 4 - 1 > w - 3 * ((w + 3) / 4)) ? (w + 3) / 4 - 1 : w - 3 * ((w + 3) / 4));
+}
+static_assert(split_rounds_for(2 * J2_GW - 1) == 2, "the bracket is meant to be finished in 2 rounds");
+
+// ROUNDS 4-ary rounds of the split search: the first i in [lo, hi] with i == hi || sA[i] > sB[dd-1-i]
+// (ties: A first) — 3 independent probes per round, a select chain instead of branches
+template <int ROUNDS>
+__device__ __forceinline__ void split_rounds(const u64* sA, const u64* sB, int dd, int& lo, int& hi) {
 #pragma unroll
-    for (int r = 0; r < LD::SEARCH_ROUNDS; r++) {
+    for (int r = 0; r < ROUNDS; r++) {
         const int w = hi - lo;
         const int s = (w + 3) >> 2;
         const int p1 = lo + s - 1, p2 = p1 + s, p3 = p2 + s;
@@ -308,33 +314,151 @@ __device__ __forceinline__ void tile_walk(const u64* sA, const u64* sB, const Ti
         lo = w > 0 ? nlo : lo;
         hi = w > 0 ? nhi : hi;
     }
-    {
-        int ia = lo, jb = dd - lo;
-        const int amax = na > 0 ? na - 1 : 0, bmax = nbx > 0 ? nbx - 1 : 0;
-        u64 ka = sA[ia < amax ? ia : amax], kb = sB[jb < bmax ? jb : bmax];
-        bool ap_ok = ia > 0 || q.has_lbA, bp_ok = jb > 0 || q.has_lbB;
-        u64 ap = sA[ia - 1];  // the A / B keys before the walk position (sA[-1] / sB[-1]: the
-        u64 bp = sB[jb - 1];  // lookbehind keys, staged with the tile; garbage when absent, unused)
+}
+
+// The walk over a thread's IPT items from its split ia0, the current and previous keys in registers
+// (one LDS round trip per item; the strictly-ascending check compares registers).
+// walk_items_full: every thread of the wave has all IPT items (every wave but the last of a tile
+// that ends both sides), so no per-item guard, and every choice a bitwise select: the guarded form's
+// short-circuit conditions compile to an exec-mask ladder (s_and_saveexec / s_xor / s_or_saveexec)
+// per item.
+template <int IPT>
+__device__ __forceinline__ void walk_items_full(const u64* sA, const u64* sB, const TileGeo& q, int ia0, int dd,
+                                                u32 rec[IPT], bool& bad) {
+    const int na = q.na, nb = q.nb;
+    const int nbx = nb + (q.has_la ? 1 : 0);
+    int ia = ia0, jb = dd - ia0;
+    const int amax = na > 0 ? na - 1 : 0, bmax = nbx > 0 ? nbx - 1 : 0;
+    u64 ka = sA[ia < amax ? ia : amax], kb = sB[jb < bmax ? jb : bmax];
+    bool ap_ok = (ia > 0) | q.has_lbA, bp_ok = (jb > 0) | q.has_lbB;
+    u64 ap = sA[ia - 1], bp = sB[jb - 1];
+    u32 b = 0;
 #pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const bool act = k < cnt;
-            const bool ta = jb >= nb || (ia < na && ka <= kb);
-            const bool m = jb < nbx && kb == ka;  // sB[nb] = the lookahead entry
-            const bool partner = ap_ok && ap == kb;
-            const u32 kind = !act ? R_NONE : ta ? (m ? R_MATCH : R_DEL) : (partner ? R_NONE : R_INS);
-            rec[k] = (kind << 25) | ((u32)jb << 12) | (u32)ia;
-            bad |= act && (ta ? (ap_ok && ap >= ka) : (bp_ok && bp >= kb));
-            const bool sa = act && ta, sb = act && !ta;
-            ap = sa ? ka : ap;
-            bp = sb ? kb : bp;
-            ap_ok |= sa;
-            bp_ok |= sb;
-            ia += sa;
-            jb += sb;
-            ka = sA[ia < amax ? ia : amax];
-            kb = sB[jb < bmax ? jb : bmax];
+    for (int k = 0; k < IPT; k++) {
+        const bool ta = (jb >= nb) | ((ia < na) & (ka <= kb));
+        const bool m = (jb < nbx) & (kb == ka);
+        const bool partner = ap_ok & (ap == kb);
+        const u32 kt = R_DEL + (u32)m, kf = partner ? (u32)R_NONE : (u32)R_INS;
+        rec[k] = ((ta ? kt : kf) << 25) | ((u32)jb << 12) | (u32)ia;
+        b |= (u32)(ap_ok & (ap >= ka)) & (u32)ta;
+        b |= (u32)(bp_ok & (bp >= kb)) & (u32)!ta;
+        ap = ta ? ka : ap;
+        bp = ta ? bp : kb;
+        ap_ok |= ta;
+        bp_ok |= !ta;
+        ia += ta;
+        jb += !ta;
+        ka = sA[ia < amax ? ia : amax];
+        kb = sB[jb < bmax ? jb : bmax];
+    }
+    bad |= b != 0;
+}
+
+template <int IPT>
+__device__ __forceinline__ void walk_items(const u64* sA, const u64* sB, const TileGeo& q, int ia0, int dd, int cnt,
+                                           u32 rec[IPT], bool& bad) {
+    const int na = q.na, nb = q.nb;
+    const int nbx = nb + (q.has_la ? 1 : 0);  // B keys in LDS, including the lookahead
+    int ia = ia0, jb = dd - ia0;
+    const int amax = na > 0 ? na - 1 : 0, bmax = nbx > 0 ? nbx - 1 : 0;
+    u64 ka = sA[ia < amax ? ia : amax], kb = sB[jb < bmax ? jb : bmax];
+    bool ap_ok = ia > 0 || q.has_lbA, bp_ok = jb > 0 || q.has_lbB;
+    u64 ap = sA[ia - 1];  // the A / B keys before the walk position (sA[-1] / sB[-1]: the
+    u64 bp = sB[jb - 1];  // lookbehind keys, staged with the tile; garbage when absent, unused)
+#pragma unroll
+    for (int k = 0; k < IPT; k++) {
+        const bool act = k < cnt;
+        const bool ta = jb >= nb || (ia < na && ka <= kb);
+        const bool m = jb < nbx && kb == ka;  // sB[nb] = the lookahead entry
+        const bool partner = ap_ok && ap == kb;
+        const u32 kind = !act ? R_NONE : ta ? (m ? R_MATCH : R_DEL) : (partner ? R_NONE : R_INS);
+        rec[k] = (kind << 25) | ((u32)jb << 12) | (u32)ia;
+        bad |= act && (ta ? (ap_ok && ap >= ka) : (bp_ok && bp >= kb));
+        const bool sa = act && ta, sb = act && !ta;
+        ap = sa ? ka : ap;
+        bp = sb ? kb : bp;
+        ap_ok |= sa;
+        bp_ok |= sb;
+        ia += sa;
+        jb += sb;
+        ka = sA[ia < amax ? ia : amax];
+        kb = sB[jb < bmax ? jb : bmax];
+    }
+}
+
+// Merge path of one tile out of LDS, branch-free (selects instead of divergent branches: SALU
+// exec-mask traffic was the join's largest instruction stream): the thread's split, then the walk.
+// Outcome per item:
+//   rec = kind << 25 | changed << 24 | jb << 12 | ia          (tile-local indices)
+// The split (j2_walk option, wave-uniform `guided`): a thread's split on diagonal dd lies near
+// g = dd * na / (na + nb) — the sides of a tile differ by its few inserts and deletes — so the search
+// first verifies the bracket [g - W, g + W - 1] (the monotone predicate false just below it and true at
+// its top: one round trip, both ends' reads issued together) and finishes inside it in 2 rounds.  A
+// wave with any lane outside its bracket runs the blind search (5 rounds for a 1024-item tile), as
+// every wave does without the option: on sorted input the predicate is monotone and both find the
+// same split.
+template <int NT, int IPT>
+__device__ __forceinline__ void tile_walk(const u64* sA, const u64* sB, const TileGeo& q, bool guided, u32 rec[IPT],
+                                          bool& bad) {
+    using LD = Join2Lds<NT, IPT>;
+    const int tid = threadIdx.x, na = q.na, nb = q.nb;
+    const int nitems = na + nb;
+    const int dd = tid * IPT < nitems ? tid * IPT : nitems;
+    const int cnt = (dd + IPT < nitems ? dd + IPT : nitems) - dd;
+    int lo = dd - nb > 0 ? dd - nb : 0, hi = dd < na ? dd : na;
+    bool blind = true;
+    if (guided || (KD_J2_PROBE & 1)) {
+        constexpr int W = J2_GW;
+        // (any guess is a valid one: the reciprocal's rounding only moves the bracket)
+        int g = (int)((float)dd * ((float)na * __builtin_amdgcn_rcpf((float)(nitems > 0 ? nitems : 1))) + 0.5f);
+        g = g < lo ? lo : g > hi ? hi : g;
+        const int L = g - W > lo ? g - W : lo, H = g + W - 1 < hi ? g + W - 1 : hi;
+        if (KD_J2_PROBE & 1) {
+            lo = hi = g;
+            blind = false;
+        } else {
+            // indices inside [lo, hi - 1] where the bracket's end is not the range's own (then unused)
+            const int hm = hi > lo ? hi - 1 : lo;
+            const int xl = L > lo ? L - 1 : lo, xh = H < hm ? H : hm;
+            const u64 al = sA[xl], vl = sB[dd - 1 - xl], ah = sA[xh], vh = sB[dd - 1 - xh];
+            const bool in = ((L <= lo) | !(al > vl)) & ((H >= hi) | (ah > vh));
+            if (__ballot(!in) == 0) {
+                lo = L;
+                hi = H;
+                split_rounds<split_rounds_for(2 * W - 1)>(sA, sB, dd, lo, hi);
+                blind = false;
+            }
         }
     }
+    if (blind) split_rounds<LD::SEARCH_ROUNDS>(sA, sB, dd, lo, hi);
+#if KD_J2_PROBE & 8
+#pragma unroll
+    for (int k = 0; k < IPT; k++) rec[k] = (u32)(lo & 0) | (u32)(cnt & 0);  // no item: no record, nothing compared
+#else
+    if (guided && __ballot(cnt != IPT) == 0) walk_items_full<IPT>(sA, sB, q, lo, dd, rec, bad);
+    else walk_items<IPT>(sA, sB, q, lo, dd, cnt, rec, bad);
+#endif
+}
+
+// Complete order check of one staged range, straight-line: thread t compares keys [t * IPT,
+// t * IPT + IPT) of the range with their predecessors (the first key against the lookbehind key), so
+// the NT threads cover every adjacent pair of a range of up to NT * IPT keys.  Reads (range_keys) and
+// compares (keys_unsorted) are apart so that the reads go out with the split search's first reads
+// and cost no round trip of their own.
+template <int IPT>
+__device__ __forceinline__ void range_keys(const u64* s, int n, u64 k[IPT + 1]) {
+    const int x0 = (int)threadIdx.x * IPT - 1, last = n > 0 ? n - 1 : 0;
+#pragma unroll
+    for (int j = 0; j <= IPT; j++) k[j] = s[x0 + j < last ? x0 + j : last];  // (s[-1]: the lookbehind key)
+}
+
+template <int IPT>
+__device__ __forceinline__ bool keys_unsorted(const u64 k[IPT + 1], int n, bool has_lb) {
+    const int x0 = (int)threadIdx.x * IPT - 1;
+    bool bad = false;
+#pragma unroll
+    for (int j = 1; j <= IPT; j++) bad |= (x0 + j < n) & ((x0 + j > 0) | has_lb) & (k[j - 1] >= k[j]);
+    return bad;
 }
 
 // Rows of the tile's matched pairs in the OID (and filename-offset) arrays: the sorted indices, or
@@ -568,12 +692,23 @@ __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
     const u64* sB = (const u64*)((const u8*)(s_ch + r.c1) + r.kb.skew) + q.has_lbB;
     u32 rec[IPT];
     bool bad = false;
-    tile_walk<NT, IPT>(sA, sB, q, rec, bad);
     // complete order check: the walk only compares the keys it consumes, and on unsorted input the
     // per-thread merge-path splits can skip keys, so every adjacent pair of the tile's two ranges
-    // (the first against the lookbehind key) is checked here as well
-    for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
-    for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
+    // (the first against the lookbehind key) is checked as well — ahead of the walk in the
+    // straight-line form (its reads go out with the split search's first), after it as two loops
+    const bool walk1 = g.walk != 0;  // (uniform)
+    const bool check1 = walk1 && !(KD_J2_PROBE & 2);
+    u64 ca[IPT + 1], cb[IPT + 1];
+    if (check1) { range_keys<IPT>(sA, q.na, ca); range_keys<IPT>(sB, q.nb, cb); }
+    tile_walk<NT, IPT>(sA, sB, q, walk1, rec, bad);
+    if (check1) {
+        bad |= keys_unsorted<IPT>(ca, q.na, q.has_lbA);
+        bad |= keys_unsorted<IPT>(cb, q.nb, q.has_lbB);
+    }
+    if (!walk1 && !(KD_J2_PROBE & 2)) {
+        for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
+        for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
+    }
     u32 ra[IPT], rb[IPT];
     // the matched pairs' name offsets, issued with the OID loads: low words only (differences of
     // offsets inside one tile's names fit 32 bits, and modular arithmetic gives them exactly)
@@ -597,7 +732,7 @@ __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
         const u32 ob = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_oid;
         const u32 baseA = ob + roA.skew, baseB = ob + 16 * roA.nch + roB.skew;
 #pragma unroll
-        for (int k = 0; k < IPT; k++) {
+        for (int k = 0; k < IPT && !(KD_J2_PROBE & 4); k++) {
             const bool m = (rec[k] >> 25) == R_MATCH;
             const u32 pa = baseA + 20 * (m ? (rec[k] & 0xFFF) : 0), pb = baseB + 20 * (m ? ((rec[k] >> 12) & 0xFFF) : 0);
             u32 d = 0;
@@ -753,7 +888,7 @@ __global__ __launch_bounds__(NT) void k_join2r(Join2Args g) {
         const u64* sB = (const u64*)((const u8*)(s_ch + cur.r.c1) + cur.r.kb.skew) + q.has_lbB;
         u32 rec[IPT];
         bool bad = false;
-        tile_walk<NT, IPT>(sA, sB, q, rec, bad);
+        tile_walk<NT, IPT>(sA, sB, q, g.walk != 0, rec, bad);
         for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
         for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
         {
@@ -1115,7 +1250,7 @@ __global__ __launch_bounds__(NT) void k_join3(Join3Args g3) {
     const u64* sB = (const u64*)((const u8*)(s_ch + r.c1) + r.kb.skew) + q.has_lbB;
     const u64* sK = (const u64*)((const u8*)s_k + rk.skew) + has_lbK;
     u32 rec[IPT];
-    tile_walk<NT, IPT>(sA, sB, q, rec, bad);
+    tile_walk<NT, IPT>(sA, sB, q, g.walk != 0, rec, bad);
     for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
     for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
     // the ancestor strictly ascending: every adjacent pair (x-1, x) with x in [k0, k1) once over all tiles
@@ -1542,7 +1677,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     const u32* sOrdT = (const u32*)((const u8*)(s_ord + roO.nch) + roT.skew);
     const u32* sOrdK = (const u32*)((const u8*)(s_ord + roO.nch + roT.nch) + roK.skew);
     u32 rec[IPT];
-    tile_walk<NT, IPT>(sA, sB, q, rec, bad);
+    tile_walk<NT, IPT>(sA, sB, q, g.walk != 0, rec, bad);
     for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
     for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
     if (lk) {
@@ -1857,6 +1992,7 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
     g.out_delta = g.out_upd = nullptr; g.counts = d_counts;
     g.stage_dkey = g.out_dkey = g.out_ukey = nullptr;
     g.ntiles = ntiles;
+    g.walk = ctx->opt.j2_walk;
     a.K = kK; a.oidK = (const u8*)P(K.oid, nK); a.nameK = (const u8*)P(K.name, nK);
     a.nameOffK = (const u64*)P(K.name_off, nK); a.ordK = (const u32*)P(ordK, nK); a.nK = nK;
     a.apart = (const u64*)apart; a.stage_conf = (u32*)sconf; a.stage_md = (uint2*)smd;
@@ -1988,6 +2124,7 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
     g.stage_dkey = (u64*)skd;
     g.out_dkey = d_dkey; g.out_ukey = d_upd ? d_ukey : nullptr;
     g.ntiles = ntiles;
+    g.walk = ctx->opt.j2_walk;
     rc = launch(ctx, "k_join2", [&] {
 #define KD_J2(U, H, P) hipLaunchKernelGGL((k_join2<C2_NT, C2_IPT, U, H, P>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, g)
 #define KD_J2OL(U) hipLaunchKernelGGL((k_join2<C2_NT, C2_IPT, U, false, false, true>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, g)

@@ -320,6 +320,7 @@ const OptDef OPTS[] = {
     {"j3_v", "KD_J3_V", nullptr, &kd_opts::j3_v, nullptr},
     {"j2_oidlds_min", "KD_J2_OIDLDS_MIN", nullptr, nullptr, &kd_opts::j2_oidlds_min},
     {"j2r", "KD_J2R", nullptr, &kd_opts::j2r, nullptr},
+    {"j2_walk", "KD_J2_WALK", nullptr, &kd_opts::j2_walk, nullptr},
     {"fd_stream", "KD_FD_STREAM", nullptr, &kd_opts::fd_stream, nullptr},
     {"fd_walk", "KD_FD_WALK", nullptr, &kd_opts::fd_walk, nullptr},
     {"pkm_max_blocks", "KD_PKM_MAX_BLOCKS", nullptr, nullptr, &kd_opts::pkm_max_blocks},

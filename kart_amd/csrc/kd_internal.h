@@ -72,6 +72,7 @@ struct kd_opts {
     int j3_v = 1;                    // KD_J3_V: 1 = k_join3b (one DMA batch per tile), 0 = k_join3
     uint64_t j2_oidlds_min = 1ull << 26;  // KD_J2_OIDLDS_MIN: k_join2 stages OIDs in LDS from this many entries
     int j2r = 0;                     // KD_J2R: 1 = the persistent register-prefetched k_join2r
+    int j2_walk = 1;                 // KD_J2_WALK: 1 = the tile's guided split search and straight-line walk / checks, 0 = the blind search
     int fd_stream = -1;              // KD_FD_STREAM: -1 auto, 0 windowed k_fielddiff, 1 streamed k_fielddiff_s
     int fd_walk = -1;                // KD_FD_WALK: -1 / 0 off, 1 the walked k_fdwalk (A/B)
     uint64_t pkm_max_blocks = 1ull << 26;  // KD_PKM_MAX_BLOCKS: largest pk range (64-pk blocks) of the bitmap pk order
