@@ -165,6 +165,10 @@ int kd_set_stream(kd_ctx* ctx, void* hip_stream);
  *   step_overlap_min [KD_STEP_OVERLAP_MIN] the side stream is used from this many entries of both sides
  *                                      together (2^26: below, the two cross-stream waits cost more than a
  *                                      short field diff hides)
+ *   step_count     [KD_STEP_COUNT]     1 (default): where kd_diff2_step uses the side stream and the field diff
+ *                                      reads update-order arenas, the field diff takes the update count from
+ *                                      partial counters the join leaves and is queued directly behind the join;
+ *                                      the group scan leads the side stream.  0: the scan in front of the fork
  *   pkm_wave       [KD_PKM_WAVE]       the bitmap pk order's scans in their LDS-free one-wave-per-chunk form:
  *                                      -1 on kd_diff2_step's side stream only, 0 never, 1 always */
 int kd_set_option(kd_ctx* ctx, const char* name, int64_t value);
@@ -450,7 +454,8 @@ typedef struct kd_step {
 /* Results are those of the separate calls in sequence, bit for bit.  The library owns the schedule: with
  * the step_overlap option the placement (k_place2) and the pk order run on a stream of the context's own
  * beside the field diff, which needs neither (a field diff given d_pairs reads the placed updates: then
- * only the pk order runs beside it; KD_DIFF_UNORDERED, or nothing to overlap: one stream).  The context's
+ * only the pk order runs beside it; KD_DIFF_UNORDERED, or nothing to overlap: one stream), and with the
+ * step_count option the group scan that writes d_counts runs there too.  The context's
  * stream waits for that work before the call returns, so whatever is queued on it next — kd_sync
  * included — comes after the whole step.  Asynchronous. */
 int kd_diff2_step(kd_ctx* ctx, const kd_step* step);

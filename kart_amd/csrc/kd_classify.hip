@@ -460,7 +460,7 @@ int kd_reserve(kd_ctx* ctx, uint64_t max_entries_per_side, uint64_t max_updates)
     int rc;
     if ((rc = ensure(ctx, "c2.part", (ntiles + 1) * 8, &p))) return rc;
     if ((rc = ensure(ctx, "c2.tcnt", ntiles * 16, &p))) return rc;
-    if ((rc = ensure(ctx, "c2.gsum", 2 * (ntiles / 64 + 1) * 8, &p))) return rc;
+    if ((rc = ensure(ctx, "c2.gsum", (2 * (ntiles / 64 + 1) + C2_UCNT * C2_UCNT_STRIDE) * 8, &p))) return rc;
     if ((rc = ensure(ctx, "c2.sdel", ntiles * (C2_TILE + 64) * 8, &p))) return rc;
     (void)max_updates;
     return KD_OK;
@@ -512,10 +512,19 @@ int kd_diff2_device_ex(kd_ctx* ctx, const kd_side* base, const kd_side* target, 
 // The whole step behind one call, so that the library sees the dependencies between its parts:
 //   k_partition2 -> k_join2 -> k_gscan2 -> k_place2 -> k_fielddiff -> pk order (deltas) -> pk order (updates)
 // is today's order on one stream, but the field diff of update-order arenas reads only the blobs and
-// the update count (k_gscan2's), and the placement and the pk order write only the record lists, the
-// key lists and the pk outputs.  With the step_overlap option the step forks after k_gscan2 (after
-// k_place2 when the field diff reads the pairs it writes): the tail runs on the context's side stream
-// beside the field diff, and the calling stream waits for it before the call returns.
+// the update count, and the placement and the pk order write only the record lists, the key lists and
+// the pk outputs.  With the step_overlap option the step forks and the tail runs on the context's
+// side stream beside the field diff; the calling stream waits for it before the call returns.  Where
+// it forks:
+//   - step_count 1, update-order arenas: directly behind k_join2.  The field diff takes the update
+//     count as the sum of the join's partial counters (c2.gsum's tail); k_gscan2, whose prefixes only
+//     k_place2 needs, leads the side stream in its LDS-free one-wave form (k_gscan2w: the field diff's
+//     resident grid holds every CU's LDS, and the block-wide scan would wait for it to drain).
+//     d_counts is then written on the side stream: it is complete only after the join back, like
+//     the lists.  The partial counters are zeroed by the next step's k_partition2, which is ordered
+//     after the join back and so after this field diff.
+//   - step_count 0: behind k_gscan2; the field diff reads d_counts[1].
+//   - a field diff given pairs reads the update list k_place2 writes: behind k_place2 either way.
 int kd_diff2_step(kd_ctx* ctx, const kd_step* s) {
     KD_CHECK(ctx && s, "kd_diff2_step: NULL");
     int rc;
@@ -534,15 +543,28 @@ int kd_diff2_step(kd_ctx* ctx, const kd_step* s) {
     if ((rc = device_zeros(ctx, &dz))) return rc;  // (first use fills it on this stream: before any fork)
     const u32* oa = s->base_order ? (s->base->n ? s->base_order : (const u32*)dz) : nullptr;
     const u32* ob = s->target_order ? (s->target->n ? s->target_order : (const u32*)dz) : nullptr;
+    const int ov = ctx->opt.step_overlap;
+    // A field diff given pairs reads d_upd: the placement then stays in front of it and only the pk
+    // order can go aside.  Nothing aside without a field diff to run beside, without a placement
+    // (KD_DIFF_UNORDERED, two empty sides), or with nothing to put there.
+    const bool place_aside = !(have_fd && s->d_pairs);
+    const bool placed = !(s->flags & KD_DIFF_UNORDERED) && s->base->n + s->target->n > 0;  // (= pl.needed)
+    // (and not below step_overlap_min entries: a short field diff hides less than the two
+    // cross-stream waits cost — C2 measured 0.243 -> 0.247 ms, kd_internal.h)
+    const bool overlap = ov > 0 && have_fd && placed && (place_aside || have_dpk || have_upk) &&
+                         s->base->n + s->target->n >= ctx->opt.step_overlap_min;
+    // the scan aside too: the field diff reads the join's partial counters instead of d_counts[1]
+    const bool scan_aside = overlap && place_aside && ctx->opt.step_count > 0;
     Diff2Place pl;
     if ((rc = diff2_front(ctx, s->base, s->target, s->flags, s->d_delta, s->d_upd, s->d_counts, s->d_err, oa, ob,
-                          s->d_delta_key, s->d_upd_key, &pl)))
+                          s->d_delta_key, s->d_upd_key, &pl, scan_aside)))
         return rc;
-    const int ov = ctx->opt.step_overlap;
+    if (!scan_aside && (rc = diff2_scan(ctx, pl, false))) return rc;
     auto field_diff = [&]() -> int {
-        return have_fd ? kd_fielddiff(ctx, s->old_blobs, s->new_blobs, s->d_pairs, s->upd_cap, s->d_counts + 1,
-                                      KD_MEM_DEVICE, s->maps, s->d_masks, s->d_status, KD_MEM_DEVICE)
-                       : KD_OK;
+        if (!have_fd) return KD_OK;
+        return fielddiff_device(ctx, s->old_blobs, s->new_blobs, s->d_pairs, s->upd_cap,
+                                scan_aside ? pl.ucnt : s->d_counts + 1, scan_aside ? (int)C2_UCNT : 0, KD_MEM_DEVICE,
+                                s->maps, s->d_masks, s->d_status, KD_MEM_DEVICE);
     };
     auto pk_orders = [&](bool lds_free) -> int {
         int r = KD_OK;
@@ -554,14 +576,6 @@ int kd_diff2_step(kd_ctx* ctx, const kd_step* s) {
                                s->pk_hi, s->d_upd_pk, s->d_upd_perm, lds_free);
         return r;
     };
-    // A field diff given pairs reads d_upd: the placement then stays in front of it and only the pk
-    // order can go aside.  Nothing aside without a field diff to run beside, without a placement
-    // (KD_DIFF_UNORDERED, two empty sides), or with nothing to put there.
-    const bool place_aside = !(have_fd && s->d_pairs);
-    // (and not below step_overlap_min entries: a short field diff hides less than the two
-    // cross-stream waits cost — C2 measured 0.243 -> 0.247 ms, kd_internal.h)
-    const bool overlap = ov > 0 && have_fd && pl.needed && (place_aside || have_dpk || have_upk) &&
-                         s->base->n + s->target->n >= ctx->opt.step_overlap_min;
     const int wave = ctx->opt.pkm_wave;
     if (!overlap) {
         if ((rc = diff2_place(ctx, pl)) || (rc = field_diff())) return rc;
@@ -582,7 +596,8 @@ int kd_diff2_step(kd_ctx* ctx, const kd_step* s) {
         // (ensure() inside also waits for `main` before it frees a buffer: kd::StreamScope)
         StreamScope scope(ctx, side);
         KD_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-        int r = place_aside ? diff2_place(ctx, pl) : KD_OK;
+        int r = scan_aside ? diff2_scan(ctx, pl, true) : KD_OK;
+        if (!r && place_aside) r = diff2_place(ctx, pl);
         // The pk masks: both calls run here in order on the side stream, like two calls on one
         // stream, so pkm_cur / pkm_zero_* describe the buffers as the kernels find them; the call
         // before this step was ordered before the fork, and any later call comes after the join.
@@ -598,8 +613,10 @@ int kd_diff2_step(kd_ctx* ctx, const kd_step* s) {
     }
     // The join back, on error paths too: `main` waits for everything queued on the side stream, so
     //  - any later call on the context's stream is ordered after the side work — the next step's
-    //    k_partition2 zeroes c2.gsum and its join overwrites c2.sdel / c2.skd / c2.tcnt, which this
-    //    step's k_place2 reads, and the next pk order marks the masks this one's scan cleared;
+    //    k_partition2 zeroes c2.gsum (which this step's k_gscan2 may read there) and d_counts (which
+    //    it writes), its join overwrites c2.sdel / c2.skd / c2.tcnt, which this step's k_place2
+    //    reads, and the next pk order marks the masks this one's scan cleared;
+    //  - d_counts and the record lists are complete for the caller's next work on its stream;
     //  - ensure()'s synchronise-before-realloc and kd_sync, which wait for the context's stream,
     //    still cover all of the step.
     // If an event call fails, the host waits for the side stream instead: nothing is left running

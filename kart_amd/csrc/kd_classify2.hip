@@ -26,6 +26,11 @@
 namespace kd {
 
 constexpr u64 C2_GROUP = 64;  // tiles per group sum (staged path: k_place2 offsets)
+// The update count for a reader that must not wait for k_gscan2 (kd_diff2_step's field diff, step_count
+// option): tile t adds its updates to partial counter t % C2_UCNT; the counters lie one 128-byte line
+// apart behind the group sums (so they spread over the L2 channels, and k_partition2 zeroes them
+// with the sums).  196k tiles a millisecond into one address would sit at the edge of what a channel's
+// atomic unit sustains; into 64 lines it is 3k each.  (C2_UCNT, C2_UCNT_STRIDE: kd_internal.h)
 #ifndef KD_C2_STAGE_PAD
 #define KD_C2_STAGE_PAD 32
 #endif
@@ -69,9 +74,12 @@ __device__ __forceinline__ u64 mp_search(const u64* __restrict__ A, const u64* _
 
 // The same split, starting from a guess: one round of PW probes spaced `step` apart around `guess`
 // brackets the answer (or cuts the range down to one side of the probes), then mp_search finishes
-// inside the bracket.  A 1 %-edit diff keeps each split within a few hundred entries of the
-// proportional guess, so the first round almost always brackets it: ~3 dependent rounds instead of
-// ~6 over the whole arrays.  Correct for any guess (the predicate is monotone; probes are clamped).
+// inside the bracket: ~3 dependent rounds instead of ~6 over the whole arrays when the bracket
+// holds.  It does where the edits are spread evenly (C2); on C3, whose inserts cluster at the end of
+// the walk, 99.8 % of the group ends lie more than 1024 entries from the proportional guess (standard
+// deviation 113k) and take the blind search — which costs k_partition2 22-32 of its 98-100 us
+// (a table of true splits for the guess cost most of that again).  Correct for any
+// guess (the predicate is monotone; probes are clamped).
 template <int PW>
 __device__ __forceinline__ u64 mp_search_guided(const u64* __restrict__ A, const u64* __restrict__ B, u64 d, u64 lo,
                                                 u64 hi, u64 guess, u64 step) {
@@ -161,6 +169,7 @@ struct Join2Args {
     uint2* stage_delta;  // staged path: tile-local slots of TILE records (the updates are derived by k_place2)
     u32* tile_cnt;       // staged path: [ntiles*4] inserts, updates, deletes, deltas
     u64* gsum;           // staged path: [2*ngroups] deltas | updates<<32, inserts | deletes<<32
+    u64* ucnt;           // (optional) staged path: C2_UCNT partial update counters, C2_UCNT_STRIDE apart
     uint2* out_delta;    // final lists
     uint2* out_upd;
     u64* stage_dkey;     // (optional) the join key of every staged delta record
@@ -615,6 +624,17 @@ __device__ __forceinline__ void tile_write(const u32 rec[IPT], const TileCounts&
 // The tile is staged in ONE HBM round trip: keys and OIDs of both sides go global -> LDS by LDS-DMA
 // (global_load_lds_dwordx4: 16 B per lane, the wave's 64 chunks land contiguously), all issued
 // before any use.
+// A tile's counts into its group's sums (<= 64 tiles x TILE per 32-bit half: no carry between
+// halves) and, where asked for, its updates into partial counter tile % C2_UCNT: lanes 0, 1 and 2
+// of the block, one atomic instruction (c is the same in every thread).
+__device__ __forceinline__ void tile_sums(const Join2Args& g, u64 tile, const TileCounts& c) {
+    const int tid = threadIdx.x;
+    if (tid > 2) return;
+    u64* p = tid < 2 ? g.gsum + 2 * (tile / C2_GROUP) + tid : g.ucnt ? g.ucnt + (tile % C2_UCNT) * C2_UCNT_STRIDE : nullptr;
+    const u64 v = tid == 0 ? c.tnd | (u64)c.tnu << 32 : tid == 1 ? (c.tnd - c.tnu - c.tdel) | (u64)c.tdel << 32 : c.tnu;
+    if (tid < 2 || (g.ucnt && v)) atomicAdd((unsigned long long*)p, (unsigned long long)v);
+}
+
 template <int NT, int IPT, bool UNORD, bool HASH, bool PERM, bool OL = false>
 __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
     // (HASH: filename checks compiled in; the int-key instantiation carries none of their registers)
@@ -785,16 +805,12 @@ __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
     tile_write<IPT>(rec, c, q.i0, q.j0, sd, su, sA, sB, kd, ku);
     if (!UNORD && tid == 0) {
         u32* cc = g.tile_cnt + 4 * tile;
-        const u32 tins = c.tnd - c.tnu - c.tdel;
-        cc[0] = tins;
+        cc[0] = c.tnd - c.tnu - c.tdel;
         cc[1] = c.tnu;
         cc[2] = c.tdel;
         cc[3] = c.tnd;
-        // group sums (<= 64 tiles x TILE per 32-bit half: no carry between halves)
-        u64* gs = g.gsum + 2 * (tile / C2_GROUP);
-        atomicAdd((unsigned long long*)gs, (unsigned long long)(c.tnd | (u64)c.tnu << 32));
-        atomicAdd((unsigned long long*)gs + 1, (unsigned long long)(tins | (u64)c.tdel << 32));
     }
+    if (!UNORD) tile_sums(g, tile, c);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -917,10 +933,8 @@ __global__ __launch_bounds__(NT) void k_join2r(Join2Args g) {
             cc[1] = c.tnu;
             cc[2] = c.tdel;
             cc[3] = c.tnd;
-            u64* gs = g.gsum + 2 * (tile / C2_GROUP);
-            atomicAdd((unsigned long long*)gs, (unsigned long long)(c.tnd | (u64)c.tnu << 32));
-            atomicAdd((unsigned long long*)gs + 1, (unsigned long long)(tins | (u64)c.tdel << 32));
         }
+        tile_sums(g, tile, c);
         if (!more) break;
         lds_barrier();  // every thread is done with the tile's LDS (and s_wave)
         deposit(nxt);
@@ -992,6 +1006,49 @@ __global__ __launch_bounds__(1024) void k_gscan2(const u64* __restrict__ gsum, u
         counts[1] = layout ? cd : cu;
         counts[2] = layout ? cu : cx;
         counts[3] = layout ? 0 : cd;
+    }
+}
+
+// The same scan (layout 0) by one wave without LDS, for kd_diff2_step's side stream: beside the
+// field diff, whose resident grid holds every CU's LDS for its whole run, a block that asks for LDS
+// waits for the field diff to drain (k_gscan2 there: 1.18 ms instead of 0.03, the placement and the
+// pk order behind it).  Lane l takes the groups [l * per, (l + 1) * per): it sums them, the wave
+// scans the 64 sums with shuffles, and a second pass over the same (now cached) group sums writes
+// the prefixes.  C3's 3,052 groups are 48 per lane; nobody waits for it there.
+__global__ __launch_bounds__(64) void k_gscan2w(const u64* __restrict__ gsum, u64 ngroups, u64* __restrict__ gpre,
+                                                u64* __restrict__ counts) {
+    const int lane = threadIdx.x;
+    const u32x4* g4 = (const u32x4*)gsum;
+    u32x4* p4 = (u32x4*)gpre;
+    const u64 per = (ngroups + 63) / 64;
+    const u64 k0 = (u64)lane * per, k1 = k0 + per < ngroups ? k0 + per : ngroups;
+    u64 td = 0, tu = 0, ti = 0, tx = 0;
+#pragma unroll 8
+    for (u64 k = k0; k < k1; k++) {
+        const u32x4 v = g4[k];
+        td += v.x; tu += v.y; ti += v.z; tx += v.w;
+    }
+    u64 sd = td, su = tu;  // inclusive wave scans (d, u), sums (i, x)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 yd = __shfl_up(sd, o, 64), yu = __shfl_up(su, o, 64);
+        if (lane >= o) { sd += yd; su += yu; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ti += __shfl_xor(ti, o, 64); tx += __shfl_xor(tx, o, 64); }
+    u64 pd = sd - td, pu = su - tu;  // this lane's first group's prefixes
+#pragma unroll 8
+    for (u64 k = k0; k < k1; k++) {
+        const u32x4 v = g4[k];
+        p4[k] = u32x4{(u32)pd, (u32)(pd >> 32), (u32)pu, (u32)(pu >> 32)};
+        pd += v.x;
+        pu += v.y;
+    }
+    if (lane == 63) {  // (its inclusive sums are the totals)
+        counts[0] = ti;
+        counts[1] = su;
+        counts[2] = tx;
+        counts[3] = sd;
     }
 }
 
@@ -1988,7 +2045,7 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
     g.dummy = (const u8*)dz;
     g.ordA = (const u32*)P(ordO, nO); g.ordB = (const u32*)P(ordT, nT);
     g.stage_delta = nullptr;
-    g.tile_cnt = (u32*)tcnt; g.gsum = (u64*)gsum; g.err = d_err;
+    g.tile_cnt = (u32*)tcnt; g.gsum = (u64*)gsum; g.ucnt = nullptr; g.err = d_err;
     g.out_delta = g.out_upd = nullptr; g.counts = d_counts;
     g.stage_dkey = g.out_dkey = g.out_ukey = nullptr;
     g.ntiles = ntiles;
@@ -2049,12 +2106,13 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
 int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd,
                  u64* d_counts, u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey) {
     Diff2Place pl;
-    int rc = diff2_front(ctx, A, B, flags, d_delta, d_upd, d_counts, d_err, ordA, ordB, d_dkey, d_ukey, &pl);
+    int rc = diff2_front(ctx, A, B, flags, d_delta, d_upd, d_counts, d_err, ordA, ordB, d_dkey, d_ukey, &pl, false);
+    if (!rc) rc = diff2_scan(ctx, pl, false);
     return rc ? rc : diff2_place(ctx, pl);
 }
 
 int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd, u64* d_counts,
-                u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey, Diff2Place* pl) {
+                u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey, Diff2Place* pl, bool count_upd) {
     *pl = Diff2Place{};
     const bool unord = (flags & KD_DIFF_UNORDERED) != 0;
     const u64 nA = A->n, nB = B->n, total = nA + nB;
@@ -2077,11 +2135,13 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
     if (!unord) {
         n_zero = 2 * ((ntiles + C2_GROUP - 1) / C2_GROUP);
         if ((rc = ensure(ctx, "c2.tcnt", ntiles * 4 * sizeof(u32), &tcnt))) return rc;
-        if ((rc = ensure(ctx, "c2.gsum", n_zero * sizeof(u64), &gsum))) return rc;
+        // (the partial update counters behind the group sums: one zeroing loop for both)
+        if ((rc = ensure(ctx, "c2.gsum", (n_zero + C2_UCNT * C2_UCNT_STRIDE) * sizeof(u64), &gsum))) return rc;
         if ((rc = ensure(ctx, "c2.gpre", n_zero * sizeof(u64), &gpre))) return rc;
         if ((rc = ensure(ctx, "c2.sdel", ntiles * C2_STAGE * sizeof(uint2), &sdel))) return rc;
         zero = (u64*)gsum;
     }
+    u64* ucnt = !unord && count_upd ? (u64*)gsum + n_zero : nullptr;
     void* skd = nullptr;  // the staged records' keys
     if (d_dkey && !unord && (rc = ensure(ctx, "c2.skd", ntiles * C2_STAGE * sizeof(u64), &skd))) return rc;
     void* dz;
@@ -2092,7 +2152,7 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
     rc = launch(ctx, "k_partition2", [&] {
         unsigned nb = (unsigned)((ntiles + C2_PG - 1) / C2_PG);
         hipLaunchKernelGGL(k_partition2<C2_TILE>, dim3(nb), dim3(C2_PNT), 0, ctx->stream, kA, nA, kB, nB, ntiles,
-                           (u64*)part, d_counts, d_err, zero, n_zero);
+                           (u64*)part, d_counts, d_err, zero, n_zero + (ucnt ? C2_UCNT * C2_UCNT_STRIDE : 0));
     });
     if (rc) return rc;
     Join2Args g;
@@ -2119,7 +2179,7 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
     g.ordA = nA && ordA ? ordA : (const u32*)dz;
     g.ordB = nB && ordB ? ordB : (const u32*)dz;
     g.stage_delta = (uint2*)sdel;
-    g.tile_cnt = (u32*)tcnt; g.gsum = (u64*)gsum; g.err = d_err;
+    g.tile_cnt = (u32*)tcnt; g.gsum = (u64*)gsum; g.ucnt = ucnt; g.err = d_err;
     g.out_delta = (uint2*)d_delta; g.out_upd = (uint2*)d_upd; g.counts = d_counts;
     g.stage_dkey = (u64*)skd;
     g.out_dkey = d_dkey; g.out_ukey = d_upd ? d_ukey : nullptr;
@@ -2145,17 +2205,27 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
 #undef KD_J2R
     });
     if (rc || unord) return rc;
-    rc = launch(ctx, "k_gscan2", [&] {
-        hipLaunchKernelGGL(k_gscan2, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)gsum, (u64)(n_zero / 2),
-                           (u64*)gpre, d_counts, 0);
-    });
-    if (rc) return rc;
     pl->needed = true;
     pl->ntiles = ntiles;
-    pl->sdel = sdel; pl->tcnt = tcnt; pl->gpre = gpre; pl->skd = skd;
+    pl->sdel = sdel; pl->tcnt = tcnt; pl->gsum = gsum; pl->gpre = gpre; pl->skd = skd;
+    pl->ucnt = ucnt;
+    pl->d_counts = d_counts;
     pl->d_delta = d_delta; pl->d_upd = d_upd;
     pl->d_dkey = d_dkey; pl->d_ukey = d_upd ? d_ukey : nullptr;
     return KD_OK;
+}
+
+int diff2_scan(kd_ctx* ctx, const Diff2Place& pl, bool lds_free) {
+    if (!pl.needed) return KD_OK;
+    const u64 ngroups = (pl.ntiles + C2_GROUP - 1) / C2_GROUP;
+    return launch(ctx, "k_gscan2", [&] {
+        if (lds_free)
+            hipLaunchKernelGGL(k_gscan2w, dim3(1), dim3(64), 0, ctx->stream, (const u64*)pl.gsum, ngroups, (u64*)pl.gpre,
+                               pl.d_counts);
+        else
+            hipLaunchKernelGGL(k_gscan2, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)pl.gsum, ngroups, (u64*)pl.gpre,
+                               pl.d_counts, 0);
+    });
 }
 
 int diff2_place(kd_ctx* ctx, const Diff2Place& pl) {

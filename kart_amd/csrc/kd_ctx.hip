@@ -328,6 +328,7 @@ const OptDef OPTS[] = {
     {"step_overlap", "KD_STEP_OVERLAP", nullptr, &kd_opts::step_overlap, nullptr},
     {"step_overlap_min", "KD_STEP_OVERLAP_MIN", nullptr, nullptr, &kd_opts::step_overlap_min},
     {"pkm_wave", "KD_PKM_WAVE", nullptr, &kd_opts::pkm_wave, nullptr},
+    {"step_count", "KD_STEP_COUNT", nullptr, &kd_opts::step_count, nullptr},
 };
 void opt_set(kd_opts& o, const OptDef& d, int64_t v) {
     if (d.i32) o.*(d.i32) = (int)v;

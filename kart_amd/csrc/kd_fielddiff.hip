@@ -1233,6 +1233,20 @@ constexpr int fd_stream_t() { return T; }  // tables up to this size are copied 
 typedef __attribute__((address_space(3))) void* fd_lds_vp;
 typedef const __attribute__((address_space(1))) void* fd_glb_vp;
 
+// The device-side update count of a launch (every lane of the block's one wave calls it together):
+// *p, or with n_part > 0 the sum of n_part (<= 64) partial counters 16 words apart (the join's, read
+// straight behind k_join2: kd_diff2_step's step_count schedule) — one load per lane and a wave
+// reduction, the result made wave-uniform for the scalar unit.
+__device__ __forceinline__ u64 fd_dev_count(const u64* __restrict__ p, int n_part) {
+    if (n_part <= 0) return *p;
+    const int lane = threadIdx.x & 63;
+    u64 v = lane < n_part ? p[(size_t)lane * C2_UCNT_STRIDE] : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
+    return (u64)hi << 32 | lo;
+}
+
 #ifdef KD_FD_WPE  // probe builds: a waves-per-SIMD floor (the register budget follows from it)
 #define KD_FD_ATTR __attribute__((amdgpu_waves_per_eu(KD_FD_WPE)))
 #else
@@ -1242,7 +1256,7 @@ template <int UPR, int NH, int NTL, int TM, int TG, int TS, int MR>
 __global__ __launch_bounds__(FD_NT) KD_FD_ATTR void k_fielddiff(const u8* __restrict__ od, const u64* __restrict__ ooff,
                                                      const u8* __restrict__ nd, const u64* __restrict__ noff,
                                                      const uint2* __restrict__ pairs, u64 n_upd_host,
-                                                     const u64* __restrict__ n_upd_dev, FdTab tg, FdTabOff to,
+                                                     const u64* __restrict__ n_upd_dev, int n_part, FdTab tg, FdTabOff to,
                                                      const u8* __restrict__ tab_base,
                                                      u64* __restrict__ masks, u8* __restrict__ status) {
     constexpr int NC = NH + NTL;       // chunks per blob image
@@ -1259,7 +1273,7 @@ __global__ __launch_bounds__(FD_NT) KD_FD_ATTR void k_fielddiff(const u8* __rest
     const int lane = threadIdx.x;
     const bool owner = lane < UPR;
     const bool spec = n_upd_dev && n_upd_host;
-    const u64 n_upd = n_upd_dev ? *n_upd_dev : n_upd_host;
+    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
     const u64 lim = spec ? n_upd_host : n_upd;
     const u64 end = min(lim, n_upd);
     // Rounds are assigned grid-stride.  (Handing them out by an atomic counter instead, so that a
@@ -1510,7 +1524,7 @@ __device__ __forceinline__ void fd_load_tile(FdTile& f, u64 tile, u64 n_upd, con
 template <int T, int CAPB, bool PF>
 __global__ __launch_bounds__(FD_NT) void k_fielddiff_s(const u8* __restrict__ od, const u64* __restrict__ ooff,
                                                        const u8* __restrict__ nd, const u64* __restrict__ noff,
-                                                       u64 n_upd_host, const u64* __restrict__ n_upd_dev,
+                                                       u64 n_upd_host, const u64* __restrict__ n_upd_dev, int n_part,
                                                        FdTab tg, FdTabOff to, const u8* __restrict__ tab_base,
                                                        u64* __restrict__ masks, u8* __restrict__ status) {
     static_assert(T <= FD_NT && CAPB % 512 == 0, "stream shape");
@@ -1521,7 +1535,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_s(const u8* __restrict__ od
     __shared__ u32 s_dummy;
     extern __shared__ __attribute__((aligned(16))) u8 s_tab[];
     const int lane = threadIdx.x;
-    const u64 n_upd = n_upd_dev ? min(*n_upd_dev, n_upd_host ? n_upd_host : ~0ull) : n_upd_host;
+    const u64 n_upd = n_upd_dev ? min(fd_dev_count(n_upd_dev, n_part), n_upd_host ? n_upd_host : ~0ull) : n_upd_host;
     const u64 ntiles = (n_upd + T - 1) / T;
     if ((u64)blockIdx.x >= ntiles) return;  // wave-uniform
     for (u32 i = 16 * lane; i < to.bytes; i += 16 * FD_NT) *(u32x4*)(s_tab + i) = *(gp128)(tab_base + i);
@@ -1662,7 +1676,7 @@ template <int TM, int TG, int TS>
 __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WPE))) void k_fdwalk(const u8* __restrict__ od, const u64* __restrict__ ooff,
                                                   const u8* __restrict__ nd, const u64* __restrict__ noff,
                                                   const uint2* __restrict__ pairs, u64 n_upd_host,
-                                                  const u64* __restrict__ n_upd_dev, u64 n_ent_o, u64 n_ent_n,
+                                                  const u64* __restrict__ n_upd_dev, int n_part, u64 n_ent_o, u64 n_ent_n,
                                                   FdTab tg, FdTabOff to, const u8* __restrict__ tab_base,
                                                   u64* __restrict__ masks, u8* __restrict__ status) {
     constexpr u32 TCAP = FD_NT;  // queued payload compares per round (then a lane compares alone)
@@ -1672,7 +1686,7 @@ __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WP
     extern __shared__ __attribute__((aligned(16))) u8 s_tab[];
     const int lane = threadIdx.x;
     const bool spec = n_upd_dev && n_upd_host;
-    const u64 n_upd = n_upd_dev ? *n_upd_dev : n_upd_host;
+    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
     const u64 lim = spec ? n_upd_host : n_upd;
     const u64 end = min(lim, n_upd);
     const u64 step = (u64)gridDim.x * FD_NT;
@@ -1786,11 +1800,11 @@ __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WP
 __global__ __launch_bounds__(FD_NT) void k_fielddiff_g(const u8* __restrict__ od, const u64* __restrict__ ooff,
                                                        const u8* __restrict__ nd, const u64* __restrict__ noff,
                                                        const uint2* __restrict__ pairs, u64 n_upd_host,
-                                                       const u64* __restrict__ n_upd_dev, FdTab tb,
+                                                       const u64* __restrict__ n_upd_dev, int n_part, FdTab tb,
                                                        u64* __restrict__ masks, u8* __restrict__ status) {
     const int lane = threadIdx.x;
     const bool spec = n_upd_dev && n_upd_host;
-    const u64 n_upd = n_upd_dev ? *n_upd_dev : n_upd_host;
+    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
     const u64 lim = spec ? n_upd_host : n_upd;
     for (u64 u0 = (u64)blockIdx.x * FD_NT; u0 < lim; u0 += (u64)gridDim.x * FD_NT) {
         const u64 u = u0 + lane;
@@ -1810,18 +1824,15 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_g(const u8* __restrict__ od
     }
 }
 
-}  // namespace kd
-
-using namespace kd;
-
-extern "C" int kd_fielddiff(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const uint32_t* pu, uint64_t n_upd,
-                            const uint64_t* d_n_upd, uint32_t pairs_mem, const kd_legend_maps* mp, uint64_t* masks,
-                            uint8_t* status, uint32_t out_mem) {
+int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const uint32_t* pu, uint64_t n_upd,
+                     const uint64_t* d_n_upd, int n_part, uint32_t pairs_mem, const kd_legend_maps* mp, uint64_t* masks,
+                     uint8_t* status, uint32_t out_mem) {
     KD_CHECK(ctx && ob && nb && mp && masks && status, "kd_fielddiff: NULL argument");
     KD_CHECK(mp->n_keys >= 0 && mp->words == (mp->n_keys + 63) / 64 && mp->words >= 1, "kd_fielddiff: bad words");
     KD_CHECK(mp->n_leg_old > 0 && mp->n_leg_new > 0 && mp->n_leg_old <= 4096 && mp->n_leg_new <= 4096,
              "kd_fielddiff: bad legend counts");
     KD_CHECK(d_n_upd == nullptr || out_mem == KD_MEM_DEVICE, "kd_fielddiff: device count needs device outputs");
+    KD_CHECK(n_part >= 0 && n_part <= 64 && (n_part == 0 || d_n_upd), "kd_fielddiff: bad partial counters");
     KD_HIP(hipSetDevice(ctx->device));
     int rc;
     // ---- host tables -> device ----
@@ -1951,20 +1962,20 @@ extern "C" int kd_fielddiff(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb,
     rc = launch(ctx, "k_fielddiff", [&] {
         auto args = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(FD_NT), o_end, ctx->stream, (const u8*)d_od, (const u64*)d_ooff,
-                               (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd,
+                               (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, n_part,
                                tb, to, (const u8*)dt, d_masks, d_status);
         };
         if (walk)
             hipLaunchKernelGGL((k_fdwalk<KD_FDW_SHAPE>), dim3(blocks), dim3(FD_NT), o_end, ctx->stream, (const u8*)d_od,
-                               (const u64*)d_ooff, (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd,
+                               (const u64*)d_ooff, (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, n_part,
                                (u64)ob->n, (u64)nb->n, tb, to, (const u8*)dt, d_masks, d_status);
         else if (stream)
             hipLaunchKernelGGL((k_fielddiff_s<KD_FD_SSHAPE, KD_FD_SPF>), dim3(blocks), dim3(FD_NT), o_end, ctx->stream, (const u8*)d_od,
-                               (const u64*)d_ooff, (const u8*)d_nd, (const u64*)d_noff, n_upd, d_n_upd, tb, to,
+                               (const u64*)d_ooff, (const u8*)d_nd, (const u64*)d_noff, n_upd, d_n_upd, n_part, tb, to,
                                (const u8*)dt, d_masks, d_status);
         else if (!lds_tab)
             hipLaunchKernelGGL(k_fielddiff_g, dim3(blocks), dim3(FD_NT), 0, ctx->stream, (const u8*)d_od, (const u64*)d_ooff,
-                               (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, tb, d_masks,
+                               (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, n_part, tb, d_masks,
                                d_status);
         // (mask words kept in registers: one for up to 64 union keys, else four)
         else if (small) W == 1 ? args(k_fielddiff<KD_FD_SHAPE_S, 1>) : args(k_fielddiff<KD_FD_SHAPE_S, 4>);
@@ -1977,3 +1988,12 @@ extern "C" int kd_fielddiff(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb,
     }
     return KD_OK;
 }
+
+}  // namespace kd
+
+extern "C" int kd_fielddiff(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const uint32_t* pu, uint64_t n_upd,
+                            const uint64_t* d_n_upd, uint32_t pairs_mem, const kd_legend_maps* mp, uint64_t* masks,
+                            uint8_t* status, uint32_t out_mem) {
+    return kd::fielddiff_device(ctx, ob, nb, pu, n_upd, d_n_upd, 0, pairs_mem, mp, masks, status, out_mem);
+}
+

@@ -61,6 +61,12 @@ struct PendingEv {
     hipEvent_t a, b;
 };
 
+// kd_fielddiff's body; n_part > 0: the update count is the sum of n_part (<= 64) counters 16 words
+// (C2_UCNT_STRIDE) apart at d_n_upd (the join's partial counters) instead of *d_n_upd
+int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const uint32_t* pu, uint64_t n_upd,
+                     const uint64_t* d_n_upd, int n_part, uint32_t pairs_mem, const kd_legend_maps* mp, uint64_t* masks,
+                     uint8_t* status, uint32_t out_mem);
+
 }  // namespace kd
 
 // Tuning options of a context (kd_set_option; kd_init seeds them once from the KD_* environment
@@ -86,6 +92,10 @@ struct kd_opts {
     // 20M-entry step, whose field diff runs 40 us, loses 0.004 ms of 0.243 to the two cross-stream
     // waits.  2^26 lies between the two.
     uint64_t step_overlap_min = 1ull << 26;
+    // KD_STEP_COUNT: 1 = kd_diff2_step's field diff of update-order arenas takes the update count
+    // from the join's partial counters and is queued directly behind k_join2, k_gscan2 goes to the
+    // side stream in front of k_place2 (where the side stream is used at all); 0 = k_gscan2 first
+    int step_count = 1;
     // KD_PKM_WAVE: the bitmap pk order's scans in their LDS-free one-wave-per-chunk form: -1 on
     // kd_diff2_step's side stream only, 0 never, 1 always
     int pkm_wave = -1;
@@ -236,19 +246,27 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
 int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta,
                  u32* d_upd, u64* d_counts, u32* d_err, const u32* ordA = nullptr, const u32* ordB = nullptr,
                  u64* d_dkey = nullptr, u64* d_ukey = nullptr);
-// diff2_device in two parts (kd_diff2_step queues them on different streams): the front runs
-// k_partition2, k_join2 and k_gscan2 — the counts are final after it — and fills `pl` with what the
-// placement needs; diff2_place launches k_place2 on ctx->stream (nothing to do when !pl.needed:
-// KD_DIFF_UNORDERED, or two empty sides)
+// diff2_device in three parts (kd_diff2_step queues them on different streams): the front runs
+// k_partition2 and k_join2 and fills `pl` with what the other two need; diff2_scan launches k_gscan2
+// on ctx->stream (lds_free: its one-wave form, which becomes resident beside a field diff that fills
+// every CU's LDS) — the counts are final after it — and diff2_place k_place2, which reads the scan's
+// prefixes (nothing to do when !pl.needed: KD_DIFF_UNORDERED, whose join writes the counts itself,
+// or two empty sides).  count_upd: the ordered join also adds every tile's update count into the
+// partial counters pl.ucnt (C2_UCNT of them, C2_UCNT_STRIDE words apart, zeroed by k_partition2),
+// whose sum is the update count as soon as the join has finished.
+constexpr u64 C2_UCNT = 64, C2_UCNT_STRIDE = 16;
 struct Diff2Place {
     bool needed = false;
     u64 ntiles = 0;
-    const void *sdel = nullptr, *tcnt = nullptr, *gpre = nullptr, *skd = nullptr;
+    const void *sdel = nullptr, *tcnt = nullptr, *gsum = nullptr, *gpre = nullptr, *skd = nullptr;
+    const u64* ucnt = nullptr;
+    u64* d_counts = nullptr;
     u32 *d_delta = nullptr, *d_upd = nullptr;
     u64 *d_dkey = nullptr, *d_ukey = nullptr;
 };
 int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd, u64* d_counts,
-                u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey, Diff2Place* pl);
+                u32* d_err, const u32* ordA, const u32* ordB, u64* d_dkey, u64* d_ukey, Diff2Place* pl, bool count_upd);
+int diff2_scan(kd_ctx* ctx, const Diff2Place& pl, bool lds_free);
 int diff2_place(kd_ctx* ctx, const Diff2Place& pl);
 // kd_delta_pk_order's body; lds_free: the scans in their one-wave-per-chunk form (no LDS, so they
 // become resident beside a field diff that fills every CU's LDS)
