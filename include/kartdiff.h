@@ -142,12 +142,8 @@ int kd_set_stream(kd_ctx* ctx, void* hip_stream);
 /* Tuning options of a context (A/B switches of the measured alternatives; defaults are the measured
  * optima).  kd_init seeds each from the environment variable in brackets, once; kd_set_option changes
  * it for later calls on the context.  Unknown names: KD_EINVAL.
- *   merge3_join    [KD_MERGE3_JOIN]    1: one-pass three-way join (k_join3); 0: classify2 + k_resolve3
- *   merge3_split   [KD_MERGE3_SPLIT]   1: k_join3 stages candidates, k_resolve3 applies the rule
- *   j3_ol          [KD_J3_OL]          1: k_join3 stages ours'/theirs' OIDs in LDS (sorted-form sides)
- *   j3_v           [KD_J3_V]           1: k_join3b (every tile range in one LDS-DMA batch); 0: k_join3
+ *   merge3_join    [KD_MERGE3_JOIN]    1: one-pass three-way join (k_join3b); 0: classify2 + k_resolve3
  *   j2_oidlds_min  [KD_J2_OIDLDS_MIN]  k_join2 stages OIDs in LDS from this many entries (2^26)
- *   j2r            [KD_J2R]            1: the persistent register-prefetched int-key join
  *   j2_walk        [KD_J2_WALK]        the join tile's work out of LDS: 1 (default) guided split search (a verified
  *                                      bracket around the proportional guess, the blind search when a wave's
  *                                      bracket fails), a walk without per-item guards in full waves, and in

@@ -19,6 +19,8 @@
 // completion order, key order inside each tile); no k_place2.
 // (Earlier variants — a persistent register-prefetched join, a decoupled look-back and a per-wave
 // run merge — were measured slower and removed; their numbers are in DESIGN.md §3.1.)
+// The file also holds the three-way join k_join3b (classify3 in one pass over the same tile
+// machinery) with its split kernel k_apart3b and placement k_place3.
 #include <cstdlib>
 
 #include "kd_join.h"
@@ -231,7 +233,7 @@ struct TileGeo {
 
 // wave-uniform 64-bit value into SGPRs: the tile geometry is loaded through the vector path (the
 // compiler cannot prove part[] read-only for s_load), and without this every derived address would
-// sit in VGPRs — for the current AND the prefetched tile
+// sit in VGPRs
 __device__ __forceinline__ u64 uni64(u64 x) {
     // (readfirstlane returns int: widen through u32, or bit 31 of the low half would sign-extend)
     return (u64)(u32)__builtin_amdgcn_readfirstlane((u32)x) | (u64)(u32)__builtin_amdgcn_readfirstlane((u32)(x >> 32)) << 32;
@@ -544,14 +546,7 @@ struct TileCounts {
     u32 tnd, tnu, tdel;  // tile totals: deltas, updates, deletes
 };
 
-// a workgroup barrier for LDS only: waits for this wave's LDS operations, not for its global loads
-// in flight (__syncthreads' release fence would drain those: the prefetch of a persistent kernel)
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0); vmcnt / expcnt at their maxima (no wait)
-    __builtin_amdgcn_s_barrier();
-}
-
-template <int NT, int IPT, bool LB = false>
+template <int NT, int IPT>
 __device__ __forceinline__ TileCounts tile_counts(const u32 rec[IPT], u32* s_wave) {
     TileCounts c;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -577,8 +572,7 @@ __device__ __forceinline__ TileCounts tile_counts(const u32 rec[IPT], u32* s_wav
         wx += __popcll(bx);
     }
     if (lane == 0) { s_wave[wid] = wd; s_wave[NT / 64 + wid] = wu; s_wave[2 * NT / 64 + wid] = wx; }
-    if (LB) lds_barrier();
-    else __syncthreads();
+    __syncthreads();
     u32 tnd = 0, tnu = 0, tdel = 0;
 #pragma unroll
     for (int w = 0; w < NT / 64; w++) {
@@ -813,144 +807,10 @@ __global__ __launch_bounds__(NT) void k_join2(Join2Args g) {
     if (!UNORD) tile_sums(g, tile, c);
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_join2r: the large int-key join, persistent with the next tile prefetched into registers.
-// A resident grid walks the tiles grid-stride; while tile t is walked, compared and written out
-// from LDS, tile t+1's keys and OIDs (keys + OIDs of both sides, ~28 KB) are in flight as plain
-// 16-B loads into registers (P per thread), and tile t+2's split points too.  After tile t the
-// registers go to LDS.  The barriers inside a tile are LDS-only (lds_barrier), so nothing in the
-// tile's own work waits for the prefetch — an LDS-DMA double buffer (tried in round 2) makes the
-// compiler drain every load before each LDS read.
-// ---------------------------------------------------------------------------------------------
-template <int NT, int IPT>
-struct J2RTile {
-    TileGeo q;
-    TileRanges r;
-    Range oa, ob;
-    u32 n0, n1, n2, n3;  // cumulative chunk counts: keys A, keys B, OIDs A, OIDs B
-};
-
-template <int NT, int IPT>
-__device__ __forceinline__ void j2r_plan(const Join2Args& g, u64 tile, u64 p0, u64 p1, J2RTile<NT, IPT>& T) {
-    using LD = Join2Lds<NT, IPT>;
-    T.q = tile_geo_from(g, tile, LD::TILE, p0, p1);
-    T.r = tile_ranges(g, T.q);
-    T.oa = mk_range(g.oidA, 20 * T.q.i0, 20 * T.q.i1);
-    T.ob = mk_range(g.oidB, 20 * T.q.j0, 20 * T.q.j1e);
-    T.n0 = T.r.ka.nch;
-    T.n1 = T.n0 + T.r.kb.nch;
-    T.n2 = T.n1 + T.oa.nch;
-    T.n3 = T.n2 + T.ob.nch;
-}
-
-template <int NT, int IPT>
-__global__ __launch_bounds__(NT) void k_join2r(Join2Args g) {
-    using LD = Join2Lds<NT, IPT>;
-    static_assert(LD::TILE <= 4095, "per-item records hold 12-bit local indices");
-    constexpr int P = (LD::CHK + LD::OCH + NT - 1) / NT;  // prefetched chunks per thread
-    __shared__ u32x4 s_ch[LD::CHK];
-    __shared__ u32x4 s_oid[LD::OCH];
-    __shared__ u32 s_wave[3 * NT / 64];
-    typedef __attribute__((address_space(3))) u32x4* l128;
-    typedef const __attribute__((address_space(1))) u32x4* g128;
-    const int tid = threadIdx.x;
-    const u64 ntiles = g.ntiles;
-    u64 tile = blockIdx.x;
-    if (tile >= ntiles) return;
-    J2RTile<NT, IPT> cur, nxt;
-    u32x4 buf[P];
-    auto fetch = [&](const J2RTile<NT, IPT>& T) {
-#pragma unroll
-        for (int p = 0; p < P; p++) {
-            const u32 c = tid + NT * p;
-            u64 src = 0;
-            if (c < T.n0) src = T.r.ka.base + 16ull * c;
-            else if (c < T.n1) src = T.r.kb.base + 16ull * (c - T.n0);
-            else if (c < T.n2) src = T.oa.base + 16ull * (c - T.n1);
-            else if (c < T.n3) src = T.ob.base + 16ull * (c - T.n2);
-            if (c < T.n3) buf[p] = *(g128)src;
-        }
-    };
-    auto deposit = [&](const J2RTile<NT, IPT>& T) {
-#pragma unroll
-        for (int p = 0; p < P; p++) {
-            const u32 c = tid + NT * p;
-            if (c < T.n0) *(l128)(s_ch + c) = buf[p];
-            else if (c < T.n1) *(l128)(s_ch + T.r.c1 + (c - T.n0)) = buf[p];
-            else if (c < T.n2) *(l128)(s_oid + (c - T.n1)) = buf[p];
-            else if (c < T.n3) *(l128)(s_oid + T.oa.nch + (c - T.n2)) = buf[p];
-        }
-    };
-    j2r_plan<NT, IPT>(g, tile, g.part[tile], g.part[tile + 1], cur);
-    fetch(cur);
-    deposit(cur);
-    u64 nt = tile + gridDim.x;
-    u64 np0 = 0, np1 = 0;
-    if (nt < ntiles) { np0 = g.part[nt]; np1 = g.part[nt + 1]; }
-    lds_barrier();
-    for (;;) {
-        const bool more = nt < ntiles;  // block-uniform
-        if (more) {
-            j2r_plan<NT, IPT>(g, nt, np0, np1, nxt);
-            fetch(nxt);  // in flight under this tile's work
-        }
-        const u64 nn = nt + gridDim.x;
-        u64 ap0 = 0, ap1 = 0;
-        if (more && nn < ntiles) { ap0 = g.part[nn]; ap1 = g.part[nn + 1]; }
-        // ---- tile `tile` from LDS ----
-        const TileGeo& q = cur.q;
-        if (!q.ok && tid == 0) atomicOr(g.err, 1u);
-        const u64* sA = (const u64*)((const u8*)s_ch + cur.r.ka.skew) + q.has_lbA;
-        const u64* sB = (const u64*)((const u8*)(s_ch + cur.r.c1) + cur.r.kb.skew) + q.has_lbB;
-        u32 rec[IPT];
-        bool bad = false;
-        tile_walk<NT, IPT>(sA, sB, q, g.walk != 0, rec, bad);
-        for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
-        for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
-        {
-            typedef const __attribute__((address_space(3))) u32* l32;
-            const u32 ob = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_oid;
-            const u32 baseA = ob + cur.oa.skew, baseB = ob + 16 * cur.oa.nch + cur.ob.skew;
-#pragma unroll
-            for (int k = 0; k < IPT; k++) {
-                const bool m = (rec[k] >> 25) == R_MATCH;
-                const u32 pa = baseA + 20 * (m ? (rec[k] & 0xFFF) : 0), pb = baseB + 20 * (m ? ((rec[k] >> 12) & 0xFFF) : 0);
-                u32 d = 0;
-#pragma unroll
-                for (int w = 0; w < 5; w++) d |= *(l32)(size_t)(pa + 4 * w) ^ *(l32)(size_t)(pb + 4 * w);
-                if (m && d) rec[k] |= 1u << 24;
-            }
-        }
-        if (bad) atomicOr(g.err, 1u);
-        const TileCounts c = tile_counts<NT, IPT, true>(rec, s_wave);
-        uint2* sd = g.stage_delta + tile * (u64)C2_STAGE;
-        u64* kd = g.stage_dkey ? g.stage_dkey + tile * (u64)C2_STAGE : nullptr;
-        tile_write<IPT>(rec, c, q.i0, q.j0, sd, nullptr, sA, sB, kd, nullptr);
-        if (tid == 0) {
-            u32* cc = g.tile_cnt + 4 * tile;
-            const u32 tins = c.tnd - c.tnu - c.tdel;
-            cc[0] = tins;
-            cc[1] = c.tnu;
-            cc[2] = c.tdel;
-            cc[3] = c.tnd;
-        }
-        tile_sums(g, tile, c);
-        if (!more) break;
-        lds_barrier();  // every thread is done with the tile's LDS (and s_wave)
-        deposit(nxt);
-        lds_barrier();
-        cur = nxt;
-        tile = nt;
-        nt = nn;
-        np0 = ap0;
-        np1 = ap1;
-    }
-}
-
 // Staged path, step 1: one block scans the C2_GROUP-tile group sums (exclusive prefix of deltas and
 // updates per group) and writes the totals — so each k_place2 tile reads one prefix instead of
 // summing every earlier group (which made k_place2 O(tiles x groups): 0.30 ms at C3's 195k tiles).
-// layout 0 (classify2): counts = inserts, updates, deletes, deltas; layout 1 (k_join3, where the
+// layout 0 (classify2): counts = inserts, updates, deletes, deltas; layout 1 (k_join3b, where the
 // "deltas" are conflicts, the "updates" merge deltas and the "inserts" clean paths): counts = clean,
 // conflicts, merge deltas, 0
 // GSCAN_GPT groups per thread, contiguous, all loaded by one 16-B load each before any use: one pass
@@ -1124,12 +984,11 @@ __global__ __launch_bounds__(NT) void k_place2(const uint2* __restrict__ stage_d
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------
-// k_join3: the three-way merge (libgit2 git_merge_trees, kart/merge.py:99-100) in one pass over
-// the three sorted sides.  The O∪T key union is cut into k_join2's merge-path tiles; the ancestor
+// The three-way merge (libgit2 git_merge_trees, kart/merge.py:99-100) in one pass over the three
+// sorted sides.  The O∪T key union is cut into k_join2's merge-path tiles; the ancestor
 // entries of each tile's key range — [apart[t], apart[t+1]) plus one lookahead entry, apart[t] =
-// lower_bound(ancestor, first key of tile t) (k_apart3) — are staged in LDS with the tile's keys.
+// lower_bound(ancestor, first key of tile t) (k_apart3b) — are staged in LDS with the tile's keys.
 // The tile walk pairs ours with theirs as k_join2 does; every path where they differ (one side only,
 // or different OIDs) finds its ancestor entry by an LDS binary search, loads the (at most three)
 // OIDs and applies the libgit2 rule: o == t -> clean; a == o -> theirs (merge delta); a == t ->
@@ -1148,20 +1007,8 @@ struct Join3Args {
     const u64* apart;     // [ntiles + 1]
     u32* stage_conf;      // per tile C2_STAGE slots of (a, o, t)
     uint2* stage_md;      // per tile C2_STAGE slots of (o, t)
-    const u64* nsplit;    // (k_join3b, KD_KEY_HASH) [4 * (ntiles + 1)]: name offsets around each split
+    const u64* nsplit;    // (KD_KEY_HASH) [4 * (ntiles + 1)]: name offsets around each split
 };
-#ifndef KD_J3_ACAP
-#define KD_J3_ACAP 1024   // ancestor keys of a tile staged in LDS (a longer range is searched in HBM)
-#endif
-constexpr int J3_ACAP = KD_J3_ACAP;
-#ifndef KD_J3_IPT
-#define KD_J3_IPT 3  // 768-item tiles: with the ancestor keys, four 256-thread blocks fit a CU's LDS
-#endif
-constexpr int J3_IPT = KD_J3_IPT;
-constexpr int J3_TILE = C2_NT * J3_IPT;
-#ifndef KD_J3_NAME_CH
-#define KD_J3_NAME_CH 1425  // filename bytes of a tile in LDS (C4's 24-B names of a 768-item tile + halo: ~22 KB)
-#endif
 
 // smallest p in [lo, hi] with p == hi || K[p] >= key, by groups of PW lanes (PW-ary search)
 template <int PW>
@@ -1200,28 +1047,6 @@ __device__ __forceinline__ u64 lb_guided(const u64* __restrict__ K, u64 n, u64 k
     return lb_search<PW>(K, key, nlo < pf ? nlo : pf, pf);
 }
 
-// apart[t] for t in [0, ntiles]: 8 lanes per split, guided by the proportional position
-__global__ __launch_bounds__(256) void k_apart3(const u64* __restrict__ O, u64 nO, const u64* __restrict__ T, u64 nT,
-                                                const u64* __restrict__ part, u64 ntiles, int tile_items,
-                                                const u64* __restrict__ K, u64 nK, u64* __restrict__ apart) {
-    const u64 t = ((u64)blockIdx.x * 256 + threadIdx.x) / 8;
-    if (t > ntiles) return;  // (whole 8-lane groups)
-    u64 r;
-    if (t == 0) r = 0;
-    else if (t == ntiles) r = nK;
-    else {
-        const u64 i = part[t], d = t * (u64)tile_items, j = d - i;
-        const u64 a = i < nO ? O[i] : ~0ull, b = j < nT ? T[j] : ~0ull;
-        const u64 key = a < b ? a : b;
-        // ours is the ancestor with a few edits: its index i is the ancestor rank up to the edits'
-        // running balance (a random walk of ~sqrt(edits) entries), so probes 256 apart around it
-        // bracket the answer; without ours, the proportional position
-        const u64 guess = nO ? (u64)((double)i / (double)nO * (double)nK) : (u64)((double)d / (double)(nO + nT) * (double)nK);
-        r = lb_guided<8>(K, nK, key, guess < nK ? guess : nK, 256);
-    }
-    if ((threadIdx.x & 7) == 0) apart[t] = r;
-}
-
 // a byte range into LDS by LDS-DMA: 64-chunk pieces dealt round-robin to the waves, continuing the
 // deal of earlier ranges (q0 = pieces dealt so far); returns the new count
 template <int NT>
@@ -1234,253 +1059,6 @@ __device__ __forceinline__ u32 dma_range(const Range& R, u32x4* dst, u32 q0) {
         if (c < R.nch) __builtin_amdgcn_global_load_lds((glb_vp)(R.base + 16ull * c), (lds_vp)(dst + 64 * p), 16, 0, 0);
     }
     return q0 + np;
-}
-
-// SPLIT: every differing path is staged with its ancestor entry as a candidate (a, o, t) and the
-// rule is applied by k_resolve3<HAVE_A> over the placed list (many paths per thread: the OID and
-// filename loads of the few differing paths of a tile no longer hold the tile's LDS)
-template <int NT, int IPT, bool HASH, bool PERM, bool SPLIT, bool OL = false>
-__global__ __launch_bounds__(NT) void k_join3(Join3Args g3) {
-    const Join2Args& g = g3.j;
-    using LD = Join2Lds<NT, IPT>;
-    // OL (A/B, sorted-form sides only): ours' and theirs' OIDs of the tile by LDS-DMA with the keys,
-    // so the matched pairs compare from LDS (one HBM round trip less per tile, 15 KB more LDS)
-    constexpr bool LOIDS = OL && !PERM;
-    __shared__ u32x4 s_oid[LOIDS ? LD::OCH : 1];
-    static_assert(LD::TILE <= 4095, "per-item records hold 12-bit local indices");
-    constexpr int KCH = (8 * (J3_ACAP + 2) + 16 + 15) / 16 + 4;
-    __shared__ u32x4 s_ch[LD::CHK];
-    __shared__ u32x4 s_k[KCH];
-    constexpr int NMCH = KD_J3_NAME_CH;
-    __shared__ u32x4 s_nm[HASH ? NMCH : 1];
-    // the tile's differing paths (their walk records) in path order: in hash mode the filename buffer
-    // holds them (the names are compared before), else a buffer of their own
-    __shared__ u32 s_drec_own[HASH ? 1 : LD::TILE];
-    __shared__ u32 s_wave[3 * NT / 64];
-    typedef const __attribute__((address_space(1))) u32* gp32;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const u64 tile = blockIdx.x;
-    const TileGeo q = tile_geo(g, tile, LD::TILE);
-    bool bad = !q.ok;
-    const TileRanges r = tile_ranges(g, q);
-    // the ancestor entries of the tile's key range [k0, k1) (+ the lookahead entry k1: a match of ours'
-    // last entry with theirs' lookahead has the next tile's first key) and the lookbehind key
-    const u64 k0 = uni64(g3.apart[tile]), kend = uni64(g3.apart[tile + 1]);
-    const bool kok = kend >= k0 && kend <= g3.nK;
-    bad |= !kok;
-    const u64 k1 = kok ? kend : k0;
-    const u64 k1e = k1 < g3.nK ? k1 + 1 : k1;
-    const bool has_lbK = k0 > 0;
-    const bool lk = k1e - k0 <= (u64)J3_ACAP;
-    Range rk{};
-    if (lk) rk = mk_range(g3.K, 8 * (k0 - has_lbK), 8 * k1e);
-    u64 nmA0 = 0, nmA1 = 0, nmB0 = 0, nmB1 = 0;
-    const u64 rA0 = PERM ? (q.i0 > J2_NAME_HALO ? q.i0 - J2_NAME_HALO : 0) : q.i0;
-    const u64 rA1 = PERM ? min(q.i1 + J2_NAME_HALO, g.nA) : q.i1;
-    const u64 rB0 = PERM ? (q.j0 > J2_NAME_HALO ? q.j0 - J2_NAME_HALO : 0) : q.j0;
-    const u64 rB1 = PERM ? min(q.j1e + J2_NAME_HALO, g.nB) : q.j1e;
-    if (HASH) {
-        nmA0 = g.nameOffA[rA0]; nmA1 = g.nameOffA[rA1];
-        nmB0 = g.nameOffB[rB0]; nmB1 = g.nameOffB[rB1];
-    }
-    u32 qq = dma_range<NT>(r.ka, s_ch, 0);
-    qq = dma_range<NT>(r.kb, s_ch + r.c1, qq);
-    if (lk) qq = dma_range<NT>(rk, s_k, qq);
-    Range roA{}, roB{};
-    if (LOIDS) {
-        roA = mk_range(g.oidA, 20 * q.i0, 20 * q.i1);
-        roB = mk_range(g.oidB, 20 * q.j0, 20 * q.j1e);
-        qq = dma_range<NT>(roA, s_oid, qq);
-        qq = dma_range<NT>(roB, s_oid + roA.nch, qq);
-    }
-    __syncthreads();  // vmcnt(0) + barrier: the keys have landed
-    Range rnA{}, rnB{};
-    bool lnames = false;
-    if (HASH) {
-        nmA0 = uni64(nmA0); nmA1 = uni64(nmA1); nmB0 = uni64(nmB0); nmB1 = uni64(nmB1);
-        rnA = mk_range(g.nameA, nmA0, nmA1);
-        rnB = mk_range(g.nameB, nmB0, nmB1);
-        lnames = nmA1 >= nmA0 && nmB1 >= nmB0 && (u64)rnA.nch + rnB.nch <= (u64)NMCH;
-        if (lnames) dma_range<NT>(rnB, s_nm + rnA.nch, dma_range<NT>(rnA, s_nm, 0));
-    }
-    const u64* sA = (const u64*)((const u8*)s_ch + r.ka.skew) + q.has_lbA;
-    const u64* sB = (const u64*)((const u8*)(s_ch + r.c1) + r.kb.skew) + q.has_lbB;
-    const u64* sK = (const u64*)((const u8*)s_k + rk.skew) + has_lbK;
-    u32 rec[IPT];
-    tile_walk<NT, IPT>(sA, sB, q, g.walk != 0, rec, bad);
-    for (int x = tid; x < q.na; x += NT) bad |= (x > 0 || q.has_lbA) && sA[x - 1] >= sA[x];
-    for (int x = tid; x < q.nb; x += NT) bad |= (x > 0 || q.has_lbB) && sB[x - 1] >= sB[x];
-    // the ancestor strictly ascending: every adjacent pair (x-1, x) with x in [k0, k1) once over all tiles
-    if (lk) {
-        for (int x = tid; x < (int)(k1 - k0); x += NT) bad |= (x > 0 || has_lbK) && sK[x - 1] >= sK[x];
-    } else {
-        for (u64 x = k0 + tid; x < k1; x += NT) bad |= x > 0 && g3.K[x - 1] >= g3.K[x];
-    }
-    u32 ra[IPT], rb[IPT];
-    u32 oa0[IPT], oa1[IPT], ob0[IPT], ob1[IPT];
-    tile_rows<IPT, PERM>(g, q, rec, ra, rb);
-    if (HASH && lnames) {
-        const u32* offA = (const u32*)g.nameOffA;
-        const u32* offB = (const u32*)g.nameOffB;
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const bool m = (rec[k] >> 25) == R_MATCH;
-            // unmatched items load nothing (a placeholder row could be the side's end: off[n + 1]
-            // lies past the caller's n + 1 offsets)
-            const u64 i = m ? ra[k] : 0, j = m ? rb[k] : 0;
-            oa0[k] = m ? offA[2 * i] : 0u; oa1[k] = m ? offA[2 * i + 2] : 0u;
-            ob0[k] = m ? offB[2 * j] : 0u; ob1[k] = m ? offB[2 * j + 2] : 0u;
-        }
-    }
-    if (LOIDS) {  // matched pairs' OIDs from LDS (both tile ranges landed with the keys)
-        typedef const __attribute__((address_space(3))) u32* l32;
-        const u32 ob = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_oid;
-        const u32 baseA = ob + roA.skew, baseB = ob + 16 * roA.nch + roB.skew;
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const bool m = (rec[k] >> 25) == R_MATCH;
-            const u32 pa = baseA + 20 * (m ? (rec[k] & 0xFFF) : 0), pb = baseB + 20 * (m ? ((rec[k] >> 12) & 0xFFF) : 0);
-            u32 d = 0;
-#pragma unroll
-            for (int w = 0; w < 5; w++) d |= *(l32)(size_t)(pa + 4 * w) ^ *(l32)(size_t)(pb + 4 * w);
-            if (m && d) rec[k] |= 1u << 24;
-        }
-    } else {
-        tile_oid_cmp<IPT>(g, rec, ra, rb);
-    }
-    bool ne = false;
-    if (HASH && lnames) {
-        __syncthreads();  // vmcnt(0) + barrier: the names DMA has landed
-        const u32 nm = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_nm;
-        const u32 baseA = nm + rnA.skew, baseB = nm + 16 * rnA.nch + rnB.skew;
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            if ((rec[k] >> 25) != R_MATCH) continue;
-            const u32 la = oa1[k] - oa0[k], lb = ob1[k] - ob0[k];
-            if (PERM && (ra[k] < rA0 || ra[k] >= rA1 || rb[k] < rB0 || rb[k] >= rB1))
-                ne |= !names_eq(g.nameA, g.nameOffA, ra[k], g.nameB, g.nameOffB, rb[k]);
-            else
-                ne |= la != lb || !lds_eq_bytes(baseA + (oa0[k] - (u32)nmA0), baseB + (ob0[k] - (u32)nmB0), la);
-        }
-    } else if (HASH) {
-        u32 act = 0;
-#pragma unroll
-        for (int k = 0; k < IPT; k++) act |= (u32)((rec[k] >> 25) == R_MATCH) << k;
-        ne |= names_ne_batch<IPT, 8>(g.nameA, g.nameOffA, ra, g.nameB, g.nameOffB, rb, act) != 0;
-    }
-    if (bad) atomicOr(g.err, 1u);
-    // ---- the paths where ours and theirs differ (one side only, or different OIDs): compacted into
-    //      LDS in path order, then resolved one per thread — a few per tile, so the per-item arrays
-    //      of the join do not carry ancestor state ----
-    u32 dif = 0, clean = 0;
-#pragma unroll
-    for (int k = 0; k < IPT; k++) {
-        const u32 kind = rec[k] >> 25, chg = (rec[k] >> 24) & 1;
-        dif |= (u32)(kind == R_DEL || kind == R_INS || (kind == R_MATCH && chg)) << k;
-        clean += kind == R_MATCH && !chg;  // ours == theirs: clean, nothing to record
-    }
-    static_assert(!HASH || NMCH * 16 >= 4 * LD::TILE, "the differing paths fit the name buffer");
-    u32* const s_drec = HASH ? (u32*)s_nm : s_drec_own;
-    u32 od = 0, wd = 0;
-#pragma unroll
-    for (int k = 0; k < IPT; k++) {
-        const u64 bd = __ballot((dif >> k) & 1);
-        od += __builtin_amdgcn_mbcnt_hi((u32)(bd >> 32), __builtin_amdgcn_mbcnt_lo((u32)bd, 0));
-        wd += __popcll(bd);
-    }
-    if (lane == 0) s_wave[wid] = wd;
-    __syncthreads();
-    u32 ndif = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; w++) {
-        const u32 x = s_wave[w];
-        if (w < wid) od += x;
-        ndif += x;
-    }
-#pragma unroll
-    for (int k = 0; k < IPT; k++)
-        if ((dif >> k) & 1) s_drec[od++] = rec[k];
-    __syncthreads();  // (s_wave reused below)
-    const u64 nk = k1e - k0;
-    const int rounds = nk ? 64 - __clzll((long long)nk) : 0;  // wave-uniform
-    u32 tc = 0, tm = 0;  // running conflict / merge-delta counts of the tile
-    u32* sc = g3.stage_conf + tile * (u64)C2_STAGE * 3;
-    uint2* sm = g3.stage_md + tile * (u64)C2_STAGE;
-    for (u32 c0 = 0; c0 < ndif; c0 += NT) {  // block-uniform
-        const u32 x = c0 + tid;
-        const bool act = x < ndif;
-        const u32 r0 = act ? s_drec[x] : 0u;
-        const u32 kind = r0 >> 25, ia = r0 & 0xFFF, jb = (r0 >> 12) & 0xFFF;
-        const u64 key = kind == R_INS ? sB[jb] : sA[ia];
-        // the ancestor entry: lower bound in the tile's range (LDS, or HBM for a long range)
-        u64 lo = 0, hi = act ? nk : 0;
-        for (int it = 0; it < rounds; it++) {
-            const u64 m = (lo + hi) >> 1;
-            const u64 mi = m < nk ? m : (nk ? nk - 1 : 0);
-            const u64 v = lk ? sK[mi] : g3.K[k0 + mi];
-            const bool on = lo < hi, lt = v < key;
-            lo = on && lt ? m + 1 : lo;
-            hi = on && !lt ? m : hi;
-        }
-        const bool found = act && lo < nk && (lk ? sK[lo] : g3.K[k0 + lo]) == key;
-        const u32 ik = found ? (u32)(k0 + lo) : KD_NONE;
-        const u32 io = act && kind != R_INS ? (u32)(q.i0 + ia) : KD_NONE;
-        const u32 itt = act && kind != R_DEL ? (u32)(q.j0 + jb) : KD_NONE;
-        bool md = false, cf = false;
-        if constexpr (SPLIT) {
-            cf = act;  // a candidate, resolved by k_resolve3
-        } else {
-        u32 rk3 = ik, ro = io, rt = itt;  // rows in the OID / filename arrays (PERM: through the orders)
-        if (PERM) {
-            rk3 = ik != KD_NONE ? *(gp32)(g3.ordK + ik) : KD_NONE;
-            ro = io != KD_NONE ? *(gp32)(g.ordA + io) : KD_NONE;
-            rt = itt != KD_NONE ? *(gp32)(g.ordB + itt) : KD_NONE;
-        }
-        const gp32 pk = rk3 != KD_NONE ? (gp32)(g3.oidK + 20ull * rk3) : (gp32)g.dummy;
-        const gp32 po = ro != KD_NONE ? (gp32)(g.oidA + 20ull * ro) : (gp32)g.dummy;
-        const gp32 pt = rt != KD_NONE ? (gp32)(g.oidB + 20ull * rt) : (gp32)g.dummy;
-        u32 dko = 0, dkt = 0;
-#pragma unroll
-        for (int w = 0; w < 5; w++) {
-            const u32 xk = pk[w];
-            dko |= xk ^ po[w];
-            dkt |= xk ^ pt[w];
-        }
-        if (HASH) {  // a matched ancestor path must carry the same filename (ours', else theirs')
-            const u32 act_o = ik != KD_NONE && io != KD_NONE;
-            const u32 act_t = ik != KD_NONE && itt != KD_NONE && io == KD_NONE;
-            const u32 rr[1] = {rk3}, oo[1] = {ro}, tt[1] = {rt};
-            if (__syncthreads_or((int)(act_o | act_t)))
-                ne |= (names_ne_batch<1, 8>(g3.nameK, g3.nameOffK, rr, g.nameA, g.nameOffA, oo, act_o) |
-                       names_ne_batch<1, 8>(g3.nameK, g3.nameOffK, rr, g.nameB, g.nameOffB, tt, act_t)) != 0;
-        }
-        // libgit2's rule where ours != theirs: a == o -> theirs (merge delta), a == t -> ours, else conflict
-        const bool pa = ik != KD_NONE, pO = io != KD_NONE, pT = itt != KD_NONE;
-        const bool a_eq_o = pa == pO && (!pa || dko == 0);
-        const bool a_eq_t = pa == pT && (!pa || dkt == 0);
-        md = act && a_eq_o;
-        cf = act && !a_eq_o && !a_eq_t;
-        clean += (act && !a_eq_o && a_eq_t && pO) || (md && pT);
-        }
-        u32 tot;
-        const u32 off = block_excl_scan<NT>((u32)cf | (u32)md << 16, s_wave, &tot);
-        if (cf) {
-            u32* o = sc + 3 * (tc + (off & 0xFFFF));
-            o[0] = ik; o[1] = io; o[2] = itt;
-        }
-        if (md) sm[tm + (off >> 16)] = make_uint2(io, itt);
-        tc += tot & 0xFFFF;
-        tm += tot >> 16;
-    }
-    if (ne) atomicOr(g.err, 2u);
-    const u32 tcl = block_sum<NT>(clean, s_wave);
-    if (tid == 0) {
-        u32* cc = g.tile_cnt + 4 * tile;
-        cc[0] = tcl; cc[1] = tm; cc[2] = 0; cc[3] = tc;
-        u64* gs = g.gsum + 2 * (tile / C2_GROUP);
-        atomicAdd((unsigned long long*)gs, (unsigned long long)(tc | (u64)tm << 32));
-        atomicAdd((unsigned long long*)gs + 1, (unsigned long long)tcl);
-    }
 }
 
 // staged conflicts / merge deltas -> final path-ordered positions; one wave per tile
@@ -1509,10 +1087,11 @@ __global__ __launch_bounds__(64) void k_place3(const u32* __restrict__ stage_con
 // ---------------------------------------------------------------------------------------------
 // k_join3b: the three-way join with every tile-sized range staged in one LDS-DMA round trip
 // ---------------------------------------------------------------------------------------------
-// k_join3 chains six to eight dependent memory round trips per tile (split points, then keys and
-// name bounds, then names, walk rows, OIDs and name offsets, then the differing paths' ancestor
-// rows, OIDs and names), and its 22-KB name buffer overflows on SURVEY's C4 names (12-24-character
-// text pks: ~36-B paths), sending every filename compare to HBM.  k_join3b cuts the chain to five:
+// Its predecessor (round 4's join, removed) chained six to eight dependent memory
+// round trips per tile (split points, then keys and name bounds, then names, walk rows, OIDs and
+// name offsets, then the differing paths' ancestor rows, OIDs and names), and its 22-KB name buffer
+// overflowed on SURVEY's C4 names (12-24-character text pks: ~36-B paths), sending every filename
+// compare to HBM.  k_join3b cuts the chain to five:
 //   1. the tile's two split records (k_apart3b: merge-path split, ancestor lower bound and the name
 //      arena offsets around the split, so no round trip waits on a split point to find its names);
 //   2. ONE LDS-DMA batch: ours' / theirs' / the ancestor's keys, (PERM) the three walk-row ranges
@@ -1523,7 +1102,7 @@ __global__ __launch_bounds__(64) void k_place3(const u32* __restrict__ stage_con
 //   4. per differing path (one per thread, after compaction; ancestor found by binary search in
 //      LDS, its row from LDS): the three OIDs and the ancestor's / the path's name offsets;
 //   5. the ancestor's filename (HBM window) against the path's name (LDS).
-// Results are k_join3's (same staging, same k_place3).
+// Conflicts and merge deltas are staged per tile and placed by k_place3, as described above.
 // Where the time goes (C4, 50M rows, r5 timing probes KD_J3B_STOP / KD_J3B_PROBE_NONAMES, 2.67 ms
 // in all): split records + the DMA batch 0.97 ms (~6.5 TB/s of staged bytes), + merge path and
 // matched pairs 0.53 ms (0.2 of it the filename compare), + the differing paths 1.2 ms.  SQ counters
@@ -1531,7 +1110,7 @@ __global__ __launch_bounds__(64) void k_place3(const u32* __restrict__ stage_con
 // 256-thread block both allow 4), so cutting round trips alone does not pay: staging the ancestor's
 // name offsets so its filename loads with the OIDs (one round trip less) measured 2.67 -> 2.70 ms,
 // a resident grid prefetching the next tile's split records 2.83 -> 3.21, and the split form (join
-// stages candidates, k_resolve3 resolves) 2.12 + 1.83 ms.  What paid: waves holding no differing
+// stages candidates, k_resolve3 resolves) 2.12 + 1.83 ms (both removed).  What paid: waves holding no differing
 // path skip the resolve (most: ~30 per tile), a 32-bit ancestor search, and a cheaper compare.
 #ifndef KD_J3B_IPT
 #define KD_J3B_IPT 2
@@ -1556,10 +1135,9 @@ constexpr int J3B_ACAP = KD_J3B_ACAP;
 #define KD_J3B_HALO 8  // (a 16-row halo measured the same at 512-item tiles; C4's leaf trees hold ~3)
 #endif
 constexpr u64 J3B_HALO = KD_J3B_HALO;
-#ifndef KD_J3B_PERSIST
-#define KD_J3B_PERSIST 0  // 1: a resident grid walking the tiles, the next split records prefetched (slower)
-#endif
-constexpr bool J3B_PERSIST = KD_J3B_PERSIST;
+// timing probes only (results invalid; `make probe PFLAGS=-DKD_J3B_STOP=n`): the tile ends after 1 the
+// split records and the DMA batch, 3 + the merge-path walk and order checks, 2 + the matched pairs;
+// KD_J3B_PROBE_NONAMES skips the LDS name compare
 #ifndef KD_J3B_STOP
 #define KD_J3B_STOP 0
 #endif
@@ -1628,9 +1206,7 @@ __device__ __forceinline__ bool glb_lds_name_eq(const u8* __restrict__ na, u64 a
     return true;
 }
 
-// SPLIT: the differing paths are staged as candidates (a, o, t) with the ancestor entry found in LDS
-// (no OID or filename load in the tile) and k_resolve3<HAVE_A> applies the rule over the placed list
-template <int NT, int IPT, bool HASH, bool PERM, bool SPLIT = false>
+template <int NT, int IPT, bool HASH, bool PERM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_join3b(Join3Args g3) {
     const Join2Args& g = g3.j;
     using LD = Join2Lds<NT, IPT>;
@@ -1648,21 +1224,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     __shared__ u32 s_wave[3 * NT / 64];
     typedef const __attribute__((address_space(1))) u32* gp32;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const u64 ntiles = g.ntiles;
-    u64 tile = blockIdx.x;
-    if (tile >= ntiles) return;  // block-uniform
-    // ---- 1. split records of both tile ends (later tiles': prefetched with the previous tile's DMA) ----
-    u64 p0 = g.part[tile], p1 = g.part[tile + 1];
-    u64 a0 = g3.apart[tile], a1 = g3.apart[tile + 1];
+    const u64 tile = blockIdx.x;
+    if (tile >= g.ntiles) return;  // block-uniform
+    // ---- 1. split records of both tile ends ----
+    const u64 p0 = g.part[tile], p1 = g.part[tile + 1];
+    const u64 a0 = g3.apart[tile], a1 = g3.apart[tile + 1];
     u64 nmA0 = 0, nmA1 = 0, nmB0 = 0, nmB1 = 0;
     if (HASH) {
         nmA0 = g3.nsplit[4 * tile]; nmB0 = g3.nsplit[4 * tile + 2];
         nmA1 = g3.nsplit[4 * tile + 5]; nmB1 = g3.nsplit[4 * tile + 7];
     }
     u32 err = 0;
-    for (;;) {  // persistent: tiles blockIdx.x, + gridDim.x, ...
-    const u64 tnext = tile + gridDim.x;
-    const bool more = J3B_PERSIST && tnext < ntiles;  // block-uniform
     const TileGeo q = tile_geo_from(g, tile, TILE, p0, p1);
     bool bad = !q.ok;
     const TileRanges r = tile_ranges(g, q);
@@ -1708,24 +1280,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
             qq = dma_range<NT>(rnB, s_nm + rnA.nch, qq);
         }
     }
-    // the next tile's split records, in flight with the batch (the name bounds in their own
-    // registers: this tile's are read until its end)
-    u64 xA0 = 0, xA1 = 0, xB0 = 0, xB1 = 0;
-    if (more) {
-        p0 = g.part[tnext]; p1 = g.part[tnext + 1];
-        a0 = g3.apart[tnext]; a1 = g3.apart[tnext + 1];
-        if (HASH) {
-            xA0 = g3.nsplit[4 * tnext]; xB0 = g3.nsplit[4 * tnext + 2];
-            xA1 = g3.nsplit[4 * tnext + 5]; xB1 = g3.nsplit[4 * tnext + 7];
-        }
-    }
     __syncthreads();  // vmcnt(0) + barrier: everything staged has landed
 #if KD_J3B_STOP == 1  // timing probe only (results invalid): split records + the DMA batch
     if (tid == 0) { u32* cc = g.tile_cnt + 4 * tile; cc[0] = cc[1] = cc[2] = cc[3] = 0; }
-    if (!more) break;
-    tile = tnext; nmA0 = xA0; nmA1 = xA1; nmB0 = xB0; nmB1 = xB1;
-    __syncthreads();
-    continue;
+    if (err) atomicOr(g.err, err);  // (the kernel's ordinary end)
+    return;
 #endif
     const u64* sA = (const u64*)((const u8*)s_ch + r.ka.skew) + q.has_lbA;
     const u64* sB = (const u64*)((const u8*)(s_ch + r.c1) + r.kb.skew) + q.has_lbB;
@@ -1747,9 +1306,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     if ((rec[0] ^ rec[IPT - 1]) == 0x7FFFFFFFu) err |= 8u;
     __syncthreads();
     if (tid == 0) { u32* cc = g.tile_cnt + 4 * tile; cc[0] = cc[1] = cc[2] = cc[3] = 0; }
-    if (!more) break;
-    tile = tnext; nmA0 = xA0; nmA1 = xA1; nmB0 = xB0; nmB1 = xB1;
-    continue;
+    if (err) atomicOr(g.err, err);  // (the kernel's ordinary end)
+    return;
 #endif
     // ---- 3. matched pairs: rows from LDS, then OIDs and name offsets ----
     u32 ra[IPT], rb[IPT];
@@ -1803,9 +1361,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     if (ne) err |= 2u;
     __syncthreads();
     if (tid == 0) { u32* cc = g.tile_cnt + 4 * tile; cc[0] = cc[1] = cc[2] = cc[3] = 0; }
-    if (!more) break;
-    tile = tnext; nmA0 = xA0; nmA1 = xA1; nmB0 = xB0; nmB1 = xB1;
-    continue;
+    if (err) atomicOr(g.err, err);  // (the kernel's ordinary end)
+    return;
 #endif
     // ---- the paths where ours and theirs differ, compacted in path order ----
     u32 dif = 0, clean = 0;
@@ -1879,9 +1436,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
         ik = found ? (u32)(k0 + lo) : KD_NONE;
         io = act && kind != R_INS ? (u32)(q.i0 + ia) : KD_NONE;
         itt = act && kind != R_DEL ? (u32)(q.j0 + jb) : KD_NONE;
-        if constexpr (SPLIT) {
-            cf = act;  // a candidate, resolved by k_resolve3
-        } else {
         // ---- 4. rows (LDS), then the three OIDs and the name offsets ----
         u32 rk3 = ik, ro = io, rt = itt;
         if (PERM) {
@@ -1931,7 +1485,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
         md = act && a_eq_o;
         cf = act && !a_eq_o && !a_eq_t;
         clean += (act && !a_eq_o && a_eq_t && pO) || (md && pT);
-        }  // (!SPLIT)
         }  // (a wave with differing paths)
         // path-order places of the conflicts and merge deltas: ballots within the wave, the waves'
         // counts through LDS (one barrier pair; a shuffle scan chains six LDS-latency steps)
@@ -1965,7 +1518,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
                         4u * (u32)__popcll(__ballot((clean >> 2) & 1)) + 8u * (u32)__popcll(__ballot((clean >> 3) & 1));
         if (lane == 0) s_wave[2 * (NT / 64) + wid] = wcl;
     }
-    __syncthreads();  // (also: every LDS read of this tile is done before the next tile's DMA)
+    __syncthreads();
     u32 tcl = 0;
 #pragma unroll
     for (int w = 0; w < NT / 64; w++) tcl += s_wave[2 * (NT / 64) + w];
@@ -1976,28 +1529,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
         atomicAdd((unsigned long long*)gs, (unsigned long long)(tc | (u64)tm << 32));
         atomicAdd((unsigned long long*)gs + 1, (unsigned long long)tcl);
     }
-    if (!more) break;
-    tile = tnext;
-    nmA0 = xA0; nmA1 = xA1; nmB0 = xB0; nmB1 = xB1;
-    }
     if (err) atomicOr(g.err, err);
 }
 
-// the three-way merge through k_join3 (sides device-resident; ord* non-null: late materialisation)
+// the three-way merge through k_join3b (sides device-resident; ord* non-null: late materialisation)
 int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd_side& T, u32* d_conf, uint2* d_md,
                        u64* d_counts, u32* d_err, const u32* ordK, const u32* ordO, const u32* ordT) {
     const u64 nK = K.n, nO = O.n, nT = T.n, total = nO + nT;
     const bool hash = K.key_mode == KD_KEY_HASH;
     const bool perm = ordK || ordO || ordT;
-    // merge3_split: the join stages candidates (a, o, t) and k_resolve3 applies the rule (C4, r4n:
-    // 4.02 vs 3.78 ms from walk order, 2.37 vs 2.16 presorted — the default resolves in the join)
-    const bool split = ctx->opt.merge3_split == 1;
-    const bool j3_ol = ctx->opt.j3_ol == 1;  // (sorted-form sides' OIDs staged with the keys)
-    const bool v2 = ctx->opt.j3_v != 0 && !(j3_ol && !perm);  // k_join3b
-    const int TILE = v2 ? J3B_TILE : J3_TILE;
     if (hash) KD_CHECK((nK == 0 || (K.name && K.name_off)) && (nO == 0 || (O.name && O.name_off)) &&
                        (nT == 0 || (T.name && T.name_off)), "merge3: KD_KEY_HASH needs filenames");
-    const u64 ntiles = (total + TILE - 1) / TILE;
+    const u64 ntiles = (total + J3B_TILE - 1) / J3B_TILE;
     const u64 n_zero = 2 * ((ntiles + C2_GROUP - 1) / C2_GROUP);
     void *part, *apart, *tcnt, *gsum, *gpre, *sconf, *smd, *dz;
     int rc;
@@ -2015,23 +1558,18 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
     const u64* kK = (const u64*)P(K.key, nK);
     rc = launch(ctx, "k_partition2", [&] {
         unsigned nb = (unsigned)((ntiles + C2_PG - 1) / C2_PG);
-        if (v2) hipLaunchKernelGGL(k_partition2<J3B_TILE>, dim3(nb), dim3(C2_PNT), 0, ctx->stream, kO, nO, kT, nT, ntiles,
-                                   (u64*)part, d_counts, d_err, (u64*)gsum, n_zero);
-        else hipLaunchKernelGGL(k_partition2<J3_TILE>, dim3(nb), dim3(C2_PNT), 0, ctx->stream, kO, nO, kT, nT, ntiles,
-                                (u64*)part, d_counts, d_err, (u64*)gsum, n_zero);
+        hipLaunchKernelGGL(k_partition2<J3B_TILE>, dim3(nb), dim3(C2_PNT), 0, ctx->stream, kO, nO, kT, nT, ntiles,
+                           (u64*)part, d_counts, d_err, (u64*)gsum, n_zero);
     });
     if (rc) return rc;
     void* nsplit = nullptr;
-    if (v2 && hash && (rc = ensure(ctx, "c3.nsplit", 4 * (ntiles + 1) * sizeof(u64), &nsplit))) return rc;
+    if (hash && (rc = ensure(ctx, "c3.nsplit", 4 * (ntiles + 1) * sizeof(u64), &nsplit))) return rc;
+    // (k_apart3b and k_join3b keep the event names "k_apart3" / "k_join3": the bench and the profiles read them)
     rc = launch(ctx, "k_apart3", [&] {
         const u64 lanes = 8 * (ntiles + 1);
-        if (v2)
-            hipLaunchKernelGGL(k_apart3b, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, kO, nO, kT, nT,
-                               (const u64*)part, ntiles, TILE, kK, nK, (u64*)apart, (const u64*)P(O.name_off, nO),
-                               (const u64*)P(T.name_off, nT), perm ? J3B_HALO : (u64)0, (u64*)nsplit);
-        else
-            hipLaunchKernelGGL(k_apart3, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, kO, nO, kT, nT,
-                               (const u64*)part, ntiles, TILE, kK, nK, (u64*)apart);
+        hipLaunchKernelGGL(k_apart3b, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, kO, nO, kT, nT,
+                           (const u64*)part, ntiles, J3B_TILE, kK, nK, (u64*)apart, (const u64*)P(O.name_off, nO),
+                           (const u64*)P(T.name_off, nT), perm ? J3B_HALO : (u64)0, (u64*)nsplit);
     });
     if (rc) return rc;
     Join3Args a;
@@ -2054,53 +1592,22 @@ int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd
     a.nameOffK = (const u64*)P(K.name_off, nK); a.ordK = (const u32*)P(ordK, nK); a.nK = nK;
     a.apart = (const u64*)apart; a.stage_conf = (u32*)sconf; a.stage_md = (uint2*)smd;
     a.nsplit = (const u64*)nsplit;
-    void *cand3 = nullptr, *c2 = nullptr;
-    if (split) {
-        if ((rc = ensure(ctx, "c3.cand3", (total + 1) * 12, &cand3))) return rc;
-        if ((rc = ensure(ctx, "c3.c2j", 64, &c2))) return rc;
-    }
-    auto j3b_grid = [&](const void* kern) {
-        if (!J3B_PERSIST) return (unsigned)ntiles;
-        return (unsigned)std::max<u64>(1, std::min<u64>(ntiles, (u64)ctx->n_cu * (u64)occupancy(ctx, kern, J3B_NT, 0)));
-    };
     rc = launch(ctx, "k_join3", [&] {
-#define KD_J3(H, PM, S) hipLaunchKernelGGL((k_join3<C2_NT, J3_IPT, H, PM, S>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, a)
-        if (v2) {
-#define KD_J3B(H, PM, S) hipLaunchKernelGGL((k_join3b<J3B_NT, J3B_IPT, H, PM, S>), dim3(j3b_grid((const void*)k_join3b<J3B_NT, J3B_IPT, H, PM, S>)), dim3(J3B_NT), 0, ctx->stream, a)
-            if (split) {
-                if (hash) { if (perm) KD_J3B(true, true, true); else KD_J3B(true, false, true); }
-                else { if (perm) KD_J3B(false, true, true); else KD_J3B(false, false, true); }
-            } else {
-                if (hash) { if (perm) KD_J3B(true, true, false); else KD_J3B(true, false, false); }
-                else { if (perm) KD_J3B(false, true, false); else KD_J3B(false, false, false); }
-            }
+#define KD_J3B(H, PM) hipLaunchKernelGGL((k_join3b<J3B_NT, J3B_IPT, H, PM>), dim3((unsigned)ntiles), dim3(J3B_NT), 0, ctx->stream, a)
+        if (hash) { if (perm) KD_J3B(true, true); else KD_J3B(true, false); }
+        else { if (perm) KD_J3B(false, true); else KD_J3B(false, false); }
 #undef KD_J3B
-        } else if (split) {
-            if (hash) { if (perm) KD_J3(true, true, true); else KD_J3(true, false, true); }
-            else { if (perm) KD_J3(false, true, true); else KD_J3(false, false, true); }
-        } else if (j3_ol && !perm) {
-            if (hash) hipLaunchKernelGGL((k_join3<C2_NT, J3_IPT, true, false, false, true>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, a);
-            else hipLaunchKernelGGL((k_join3<C2_NT, J3_IPT, false, false, false, true>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, a);
-        } else {
-            if (hash) { if (perm) KD_J3(true, true, false); else KD_J3(true, false, false); }
-            else { if (perm) KD_J3(false, true, false); else KD_J3(false, false, false); }
-        }
-#undef KD_J3
     });
     if (rc) return rc;
-    u64* jcounts = split ? (u64*)c2 : d_counts;
     rc = launch(ctx, "k_gscan2", [&] {
         hipLaunchKernelGGL(k_gscan2, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)gsum, (u64)(n_zero / 2),
-                           (u64*)gpre, jcounts, 1);
+                           (u64*)gpre, d_counts, 1);
     });
     if (rc) return rc;
-    rc = launch(ctx, "k_place3", [&] {
+    return launch(ctx, "k_place3", [&] {
         hipLaunchKernelGGL(k_place3, dim3((unsigned)ntiles), dim3(64), 0, ctx->stream, (const u32*)sconf,
-                           (const uint2*)smd, (const u32*)tcnt, (const u64*)gpre, split ? (u32*)cand3 : d_conf, d_md);
+                           (const uint2*)smd, (const u32*)tcnt, (const u64*)gpre, d_conf, d_md);
     });
-    if (rc || !split) return rc;
-    return resolve3_have_a(ctx, K, O, T, (const u32*)cand3, (const u64*)c2, d_conf, d_md, d_counts, d_err, ordK, ordO,
-                           ordT);
 }
 
 int diff2_device(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32* d_delta, u32* d_upd,
@@ -2171,11 +1678,6 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
     // OIDs staged in LDS from this many entries on (C3's 200M: k_join2 1.28 -> 1.20 ms; C2's 20M:
     // 0.131 -> 0.136, profiles/r03/join2_oid_lds_ab.jsonl); the j2_oidlds_min option overrides (tests)
     const bool oid_lds = nA + nB >= ctx->opt.j2_oidlds_min;
-    // j2r: the persistent register-prefetched form of the large int-key join (C3, r4o: k_join2 1.93 vs
-    // 1.18 ms — three resident tiles per CU prefetching hold fewer bytes in flight than five one-shot
-    // tiles; one tile per workgroup stays the default)
-    const bool j2r = ctx->opt.j2r == 1;
-    const int j2r_occ = j2r ? occupancy(ctx, (const void*)k_join2r<C2_NT, C2_IPT>, C2_NT, 0) : 1;
     g.ordA = nA && ordA ? ordA : (const u32*)dz;
     g.ordB = nB && ordB ? ordB : (const u32*)dz;
     g.stage_delta = (uint2*)sdel;
@@ -2188,13 +1690,11 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
     rc = launch(ctx, "k_join2", [&] {
 #define KD_J2(U, H, P) hipLaunchKernelGGL((k_join2<C2_NT, C2_IPT, U, H, P>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, g)
 #define KD_J2OL(U) hipLaunchKernelGGL((k_join2<C2_NT, C2_IPT, U, false, false, true>), dim3((unsigned)ntiles), dim3(C2_NT), 0, ctx->stream, g)
-#define KD_J2R() hipLaunchKernelGGL((k_join2r<C2_NT, C2_IPT>), dim3((unsigned)std::min<u64>(ntiles, (u64)ctx->n_cu * j2r_occ)), dim3(C2_NT), 0, ctx->stream, g)
         if (perm) {
             if (unord) { if (hash) KD_J2(true, true, true); else KD_J2(true, false, true); }
             else { if (hash) KD_J2(false, true, true); else KD_J2(false, false, true); }
         } else if (!hash && oid_lds) {
             if (unord) KD_J2OL(true);
-            else if (j2r) KD_J2R();
             else KD_J2OL(false);
         } else {
             if (unord) { if (hash) KD_J2(true, true, false); else KD_J2(true, false, false); }
@@ -2202,7 +1702,6 @@ int diff2_front(kd_ctx* ctx, const kd_side* A, const kd_side* B, u32 flags, u32*
         }
 #undef KD_J2
 #undef KD_J2OL
-#undef KD_J2R
     });
     if (rc || unord) return rc;
     pl->needed = true;

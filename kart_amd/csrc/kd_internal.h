@@ -73,11 +73,7 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
 // variables of the same names, documented in kartdiff.h).  Defaults are the measured optima.
 struct kd_opts {
     int merge3_join = 1;             // KD_MERGE3_JOIN: 0 = round 3's two-step merge (classify2 + k_resolve3)
-    int merge3_split = 0;            // KD_MERGE3_SPLIT: 1 = k_join3 stages candidates, k_resolve3 applies the rule
-    int j3_ol = 0;                   // KD_J3_OL: 1 = k_join3 stages ours'/theirs' OIDs in LDS (sorted-form sides)
-    int j3_v = 1;                    // KD_J3_V: 1 = k_join3b (one DMA batch per tile), 0 = k_join3
     uint64_t j2_oidlds_min = 1ull << 26;  // KD_J2_OIDLDS_MIN: k_join2 stages OIDs in LDS from this many entries
-    int j2r = 0;                     // KD_J2R: 1 = the persistent register-prefetched k_join2r
     int j2_walk = 1;                 // KD_J2_WALK: 1 = the tile's guided split search and straight-line walk / checks, 0 = the blind search
     int fd_stream = -1;              // KD_FD_STREAM: -1 auto, 0 windowed k_fielddiff, 1 streamed k_fielddiff_s
     int fd_walk = -1;                // KD_FD_WALK: -1 / 0 off, 1 the walked k_fdwalk (A/B)
@@ -234,12 +230,8 @@ void comm_release(kd_ctx* ctx);
 // ordA / ordB (both or neither): the sides' OIDs and filename offsets are in another order, row
 // ord[i] belongs to sorted entry i (kd_diff2_device_perm)
 // d_dkey / d_ukey (optional): the join key of every delta / update record, beside the lists
-// three-way merge in one pass (k_join3): conflicts (a, o, t) and merge deltas (o, t) in path order,
+// three-way merge in one pass (k_join3b): conflicts (a, o, t) and merge deltas (o, t) in path order,
 // counts = clean, conflicts, merge deltas, 0; ord*: late materialisation (walk rows of sorted entries)
-// k_resolve3 over k_join3's candidates (a, o, t) with the ancestor entries already found
-int resolve3_have_a(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd_side& T, const u32* cand3, const u64* c2,
-                    u32* d_conf, uint2* d_md, u64* d_counts, u32* d_err, const u32* ordK, const u32* ordO,
-                    const u32* ordT);
 int merge3_join_device(kd_ctx* ctx, const kd_side& K, const kd_side& O, const kd_side& T, u32* d_conf, uint2* d_md,
                        u64* d_counts, u32* d_err, const u32* ordK = nullptr, const u32* ordO = nullptr,
                        const u32* ordT = nullptr);

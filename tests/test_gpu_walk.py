@@ -3,6 +3,8 @@ radix-sorted into pk order (kd_delta_pk_order), the hash sides' per-bucket sort
 (kd_sort_segmented_into) and the late-materialised three-way merge — against numpy, the oracle and the
 reference's own sorted_items order (tests/golden)."""
 import ctypes
+import os
+import re
 
 import numpy as np
 import pytest
@@ -237,13 +239,10 @@ def test_gpu_diff2_ex_delta_keys_only(engine, flags):
 # every one bit-exact with the oracle on the C4 layer (sorted and walk-order forms) and, for the
 # two-way join's OID staging, on the C3 polygon layer
 OPTION_SETS = {
-    "split": {"merge3_split": 1, "j3_v": 1},   # k_join3b<SPLIT=true> stages candidates, k_resolve3 applies the rule
-    "join3_v0": {"j3_v": 0},                    # round 4's k_join3
-    "join3_v0_ol": {"j3_v": 0, "j3_ol": 1},     # k_join3 with ours'/theirs' OIDs in LDS
     "two_step": {"merge3_join": 0},             # classify2 + k_resolve3
     "oidlds": {"j2_oidlds_min": 0},             # k_join2 stages OIDs in LDS at every size
 }
-OPTION_DEFAULTS = {"merge3_split": 0, "j3_v": 1, "j3_ol": 0, "merge3_join": 1, "j2_oidlds_min": 1 << 26}
+OPTION_DEFAULTS = {"merge3_join": 1, "j2_oidlds_min": 1 << 26}
 
 
 @pytest.mark.parametrize("opts", sorted(OPTION_SETS))
@@ -285,3 +284,46 @@ def test_gpu_option_paths_vs_oracle(engine, request, opts):
     assert np.array_equal(delta, od)
     om2, ost = O.fielddiff(*L.base_blobs, *L.target_blobs, upd, maps)
     assert np.array_equal(masks, om2) and np.array_equal(status, ost)
+
+
+def _header_options():
+    """(name, KD_* variable) of every `name [KD_NAME]` line of kartdiff.h's comment on kd_set_option"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "kartdiff.h")).read()
+    comment = text[text.index("/* Tuning options of a context"):text.index("int kd_set_option(")]
+    return re.findall(r"^ \*\s+(\w+)\s+\[(KD_\w+)\]", comment, re.M)
+
+
+def _declared_defaults():
+    """the default kd_opts declares for each of its fields (kd_internal.h)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "kart_amd", "csrc", "kd_internal.h")).read()
+    body = re.search(r"^struct kd_opts \{\n(.*?)^\};", text, re.M | re.S).group(1)
+    out = {}
+    for name, value in re.findall(r"^\s*(?:int|int64_t|uint64_t)\s+(\w+)\s*=\s*([^;]+);", body, re.M):
+        assert re.fullmatch(r"[-\d\s<ul]+", value), value  # integer literals and shifts only
+        out[name] = eval(re.sub(r"(\d)(?:ull|ul|u|ll)\b", r"\1", value))
+    return out
+
+
+def test_gpu_option_table_matches_header(monkeypatch):
+    """the option comment of kartdiff.h, kd_opts and the library's option table name the same options
+    with the same defaults, and a retired or unknown option is KD_EINVAL"""
+    from kart_amd.engine import Engine
+
+    listed = _header_options()
+    defaults = _declared_defaults()
+    assert len(listed) >= 10 and len({n for n, _ in listed}) == len(listed)
+    for name, env in listed:
+        assert env == "KD_" + name.upper()
+        monkeypatch.delenv(env, raising=False)  # kd_init would seed the option from it
+    with Engine(0) as eng:  # a fresh context: nothing has set an option on it
+        for name, _ in listed:
+            assert eng.get_option(name) == defaults[name], name
+        for name in ("merge3_split", "j3_ol", "j3_v", "j2r", "no_such_option"):
+            with pytest.raises(N.KdError) as e:
+                eng.set_option(name, 1)
+            assert e.value.code == N.KD_EINVAL, name
+            with pytest.raises(N.KdError) as e:
+                eng.get_option(name)
+            assert e.value.code == N.KD_EINVAL, name
