@@ -23,6 +23,9 @@
  *                     the geometry of each delta's old/new feature blob, envelope-tested, kept
  *                     deltas compacted on the GPU.  kd_geom_heads + kd_geom_filter_heads: the same
  *                     from 48-byte geometry heads the blob reader extracts on the host.
+ *   kd_geom_refine <- SpatialFilter.matches' exact test (kart/spatial_filter/__init__.py:534-590, the
+ *                     prepared filter polygon's Intersects): the filter's candidates decided on the
+ *                     GPU wherever FP64 certifies the answer, the rest left to the caller.
  *   kd_hex_encode  <- Geometry.to_hex_wkb / gpkg_geom_to_hex_wkb (kart/geometry.py:346-375) and
  *                     bytes.hex(v), as feature_as_json formats them (kart/feature_output.py:34-56).
  *   kd_diff2_sharded / kd_diff2_gather
@@ -342,6 +345,45 @@ int kd_geom_filter_deltas(kd_ctx* ctx, const kd_geom_head* heads_old, uint64_t n
                           uint64_t n_new, const kd_blobs* old_blobs, const kd_blobs* new_blobs, const uint32_t* pairs,
                           uint64_t cap, const uint64_t* d_n, const double filt_env[4], uint32_t flags, int bits,
                           uint8_t* match, uint32_t* keep, uint64_t* n_keep, uint8_t* enc, uint8_t* enc_ok);
+
+/* The exact stage behind the envelope test: Intersects(feature, filter polygon) for the sides the
+ * filter left 1 CANDIDATE, decided on the device wherever FP64 can prove the answer.
+ *
+ * Filter: closed rings of finite XY doubles (host memory); its region is the even-odd interior of
+ * all rings together, boundary included — a valid OGC polygon's or multipolygon's point set.  Up to
+ * 2^20 vertices (more: KD_EUNSUPPORTED).  Its device copy is kept in the context and written again
+ * only when the pointer, the sizes or a hash of the bytes change.
+ *
+ * Feature: the WKB behind the GPKG header, either byte order per sub-geometry, ISO types 1-6 and
+ * their +1000 / +2000 / +3000 variants (extra ordinates ignored); a polygon is the even-odd interior
+ * of its own rings, boundary included.  Intersects holds when a vertex of the feature lies in the
+ * filter, a segment of the feature meets a boundary segment of the filter, or the feature is areal
+ * and the first vertex of a filter ring lies in it.  Every decision is an exact comparison of
+ * doubles or the sign of det = (ax-cx)(by-cy) - (ay-cy)(bx-cx) in FP64, which counts only when
+ * |det| > (3 + 16 eps) eps (|(ax-cx)(by-cy)| + |(ay-cy)(bx-cx)|), eps = 2^-53, the sum >= 1e-290 and
+ * every operand finite.  A witness makes the side 2 MATCHING; no witness and nothing undecided
+ * 0 NON_MATCHING; anything else stays 1 for the caller's exact test — every touching configuration
+ * (shared vertex, shared edge, point on the boundary) among them.  Type 7 and above, EWKB flag
+ * bits, a count that runs past the value and a non-finite coordinate stay 1 as well (counted
+ * unsupported).  No byte outside the GPKG value [goff, goff + glen) of the blob is read.
+ *
+ * heads / pairs / blobs as in kd_geom_filter_heads, flags & KD_GF_DELTA_HEADS as in
+ * kd_geom_filter_deltas (KD_GF_RECT is ignored); NULL heads: KD_EUNSUPPORTED (the geometry is not
+ * located from legends here), the arenas are required.  A side whose code is not 1, or whose head is
+ * not KD_GH_GEOM, is left untouched.  match [n * 2] is updated in place, keep [n] / *n_keep are
+ * rebuilt in delta order from the codes (either side 1, 2 or 3), stats[4] <- candidate sides decided
+ * true, decided false, left undecided, unsupported or malformed.  Host buffers (out_mem, pairs_mem,
+ * heads_mem, blobs->mem = KD_MEM_HOST), or everything device memory with the delta count read from
+ * *d_n on the device (n = capacity; match 2-B, stats 8-B aligned). */
+typedef struct kd_filter_poly {
+    const double* xy;         /* [n_vert][2], each ring closed (first vertex == last)          */
+    const uint64_t* ring_off; /* [n_ring + 1]: ring r = vertices ring_off[r] .. ring_off[r+1]  */
+    uint64_t n_ring, n_vert;
+} kd_filter_poly;
+int kd_geom_refine(kd_ctx* ctx, const kd_filter_poly* filter, const kd_geom_head* heads_old, uint64_t n_old,
+                   const kd_geom_head* heads_new, uint64_t n_new, uint32_t heads_mem, const kd_blobs* old_blobs,
+                   const kd_blobs* new_blobs, const uint32_t* pairs, uint64_t n, const uint64_t* d_n, uint32_t pairs_mem,
+                   uint32_t flags, uint8_t* match, uint32_t* keep, uint64_t* n_keep, uint64_t* stats, uint32_t out_mem);
 
 /* -------- writer formatting -------- */
 #define KD_HEX_BYTES 0u    /* bytes.hex(v): lowercase hex of every byte of every blob                */

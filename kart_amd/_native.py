@@ -148,6 +148,16 @@ class KdGeomCols(ctypes.Structure):
     ]
 
 
+class KdFilterPoly(ctypes.Structure):
+    """kd_filter_poly: the filter polygon's closed rings (host memory)"""
+    _fields_ = [
+        ("xy", ctypes.c_void_p),
+        ("ring_off", ctypes.c_void_p),
+        ("n_ring", ctypes.c_uint64),
+        ("n_vert", ctypes.c_uint64),
+    ]
+
+
 class KdKeysInfo(ctypes.Structure):
     _fields_ = [
         ("vary", ctypes.c_uint64),
@@ -248,6 +258,13 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(KdBlobs),
          ctypes.POINTER(KdBlobs), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, c_dblp, ctypes.c_uint32, ctypes.c_int,
          ctypes.c_void_p, ctypes.c_void_p, c_u64p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "kd_geom_refine": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(KdFilterPoly), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_uint32, ctypes.POINTER(KdBlobs), ctypes.POINTER(KdBlobs), ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_uint32],
     ),
     "kd_shard_cuts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

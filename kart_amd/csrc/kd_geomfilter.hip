@@ -943,6 +943,66 @@ __global__ __launch_bounds__(GF_NT) void k_gf_place(const u8* __restrict__ match
     }
 }
 
+// kept deltas per tile from finished codes (kd_geom_refine: the refine rewrote candidate sides, so
+// the kept list is rebuilt from the codes): one block per tile of the capacity, a tile past the
+// device count writes 0
+__global__ __launch_bounds__(GF_NT) void k_gf_count(const u8* __restrict__ match, u64 cap, const u64* __restrict__ d_n,
+                                                    u32* __restrict__ tile_cnt) {
+    __shared__ u32 s_w[GF_NT / 64];
+    const int tid = threadIdx.x;
+    const u64 n = d_n ? min(*d_n, cap) : cap;
+    const u64 t0 = (u64)blockIdx.x * GF_TILE;
+    u32 kept = 0;
+    for (int r = 0; r < GF_ROUNDS; r++) {
+        const u64 d = t0 + (u64)r * GF_NT + tid;
+        bool k = false;
+        if (d < n) {
+            const u16 m = *(const u16*)(match + 2 * d);
+            const u32 co = m & 0xff, cn = m >> 8;
+            k = (co >= 1 && co <= 3) || (cn >= 1 && cn <= 3);
+        }
+        kept += (u32)__popcll(__ballot(k));
+    }
+    if ((tid & 63) == 0) s_w[tid >> 6] = kept;
+    __syncthreads();
+    if (tid == 0) {
+        u32 t = 0;
+        for (int w = 0; w < GF_NT / 64; w++) t += s_w[w];
+        tile_cnt[blockIdx.x] = t;
+    }
+}
+
+// k_gf_scan for another caller (kd_geom_refine's work-list counts): cnt[0..n) scanned in place
+// (exclusive), the total to *total
+int gf_scan(kd_ctx* ctx, u32* cnt, u32 n, u64* total) {
+    return launch(ctx, "k_gf_scan", [&] { hipLaunchKernelGGL(k_gf_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, n, total); });
+}
+
+// keep[0..*nk_dst) <- the deltas with either side 1, 2 or 3, in delta order, from the codes alone
+// (k_gf_count, then the filter's own scan and placement); everything device memory
+int gf_rekeep(kd_ctx* ctx, const u8* match, u64 n, const u64* d_n, u32* keep, u64* nk_dst) {
+    int rc;
+    const u64 tiles = (n + GF_TILE - 1) / GF_TILE;
+    KD_CHECK(tiles < (1ull << 31), "gf_rekeep: too many deltas");
+    if (!tiles) {
+        KD_HIP(hipMemsetAsync(nk_dst, 0, 8, ctx->stream));
+        return KD_OK;
+    }
+    void* t_cnt;
+    if ((rc = ensure(ctx, "gf.tiles", (tiles + 1) * 4, &t_cnt))) return rc;
+    if ((rc = launch(ctx, "k_gf_count", [&] {
+             hipLaunchKernelGGL(k_gf_count, dim3((unsigned)tiles), dim3(GF_NT), 0, ctx->stream, match, n, d_n, (u32*)t_cnt);
+         })))
+        return rc;
+    if ((rc = launch(ctx, "k_gf_scan", [&] {
+             hipLaunchKernelGGL(k_gf_scan, dim3(1), dim3(1024), 0, ctx->stream, (u32*)t_cnt, (u32)tiles, nk_dst);
+         })))
+        return rc;
+    return launch(ctx, "k_gf_place", [&] {
+        hipLaunchKernelGGL(k_gf_place, dim3((unsigned)tiles), dim3(GF_NT), 0, ctx->stream, match, n, d_n, (const u32*)t_cnt,
+                           keep);
+    });
+}
 
 // Delta-order heads: delta d's old and new heads copied to slot d of two contiguous arrays (the
 // layout the drop-in's blob reader hands over: it reads the deltas' blobs after classification), and

@@ -152,6 +152,11 @@ struct kd_ctx {
     void* pin_dev[2] = {nullptr, nullptr};  // the chunks' device-side addresses (k_to_host writes them)
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     int pin_next = 0;
+    // kd_geom_refine: the filter polygon whose device copy sits in slot "gr.filter" — the host
+    // pointer, vertex and ring counts and a hash of its bytes (0 vertices: none yet)
+    const void* gr_ptr = nullptr;
+    void* gr_dev = nullptr;  // where that copy was written (a regrown slot is filled again)
+    uint64_t gr_nv = 0, gr_nr = 0, gr_hash = 0;
 };
 
 namespace kd {
@@ -223,6 +228,9 @@ int stage_in(kd_ctx* ctx, const char* slot, const void* p, size_t bytes, u32 mem
 // a side's arrays staged to device scratch slots "<tag>.*" (device sides pass through); checks
 int stage_side(kd_ctx* ctx, const kd_side* s, const char* tag, kd_side* dev);
 int check_side(const kd_side* s, const char* which);
+// kd_geomfilter.hip: the kept list rebuilt from finished codes (device memory; kd_geom_refine)
+int gf_rekeep(kd_ctx* ctx, const u8* match, u64 n, const u64* d_n, u32* keep, u64* nk_dst);
+int gf_scan(kd_ctx* ctx, u32* cnt, u32 n, u64* total);
 // destroy the context's communicators (kd_fini)
 void comm_release(kd_ctx* ctx);
 

@@ -457,15 +457,22 @@ class FilterPipeline:
     whole layer in one stream."""
 
     def __init__(self, engine, base, target, base_blobs, target_blobs, geom_cols, filt_env, rectangle=False, bits=20,
-                 heads=False, delta_order=False, gather=False):
+                 heads=False, delta_order=False, gather=False, polygons=None):
         """heads: filter from 48-B geometry heads (the blob reader's host pass) instead of the blob
         arenas; delta_order (with heads): the heads in delta order, as the drop-in's blob reader lays
         them out after classification (it reads the deltas' blobs) — built once on the host from the
         deltas of a first diff (``delta_heads_s``), then every step is classify2 + the filter over them
         (kd_geom_filter_deltas, KD_GF_DELTA_HEADS; the blob fallback through the step's delta pairs);
         gather (with delta_order): the per-entry heads are instead gathered into delta order on the
-        device inside every step (k_gh_gather)"""
+        device inside every step (k_gh_gather);
+        polygons (needs heads): the filter geometry's rings ([polygon][ring][(x, y)], or a SpatialFilter
+        that carries them) — every step then decides its candidate sides against them on the device
+        (kd_geom_refine) behind the envelope filter; ``results()`` keeps its shape, ``refine_stats()``
+        gives the last step's counters"""
         import ctypes as _c
+
+        if polygons is not None and not heads:
+            raise ValueError("FilterPipeline: polygons needs heads=True (the refine locates the geometry by its head)")
 
         self.eng = engine
         self.A, self.B = DevSide(engine, base), DevSide(engine, target)
@@ -495,6 +502,19 @@ class FilterPipeline:
         self.gather = bool(gather) and self.delta_order
         self.dheads = None
         self.delta_heads_s = None
+        self._poly = None
+        if polygons is not None:
+            from .spatial import SpatialFilter
+
+            sf = polygons if isinstance(polygons, SpatialFilter) else SpatialFilter.from_polygons(polygons)
+            self._poly_xy, self._poly_off = sf.polygon_arrays()  # (kept alive: the native side keys on the address)
+            self._poly = N.KdFilterPoly()
+            self._poly.xy = N.ptr(self._poly_xy)
+            self._poly.ring_off = N.ptr(self._poly_off)
+            self._poly.n_ring = int(self._poly_off.shape[0]) - 1
+            self._poly.n_vert = int(self._poly_xy.shape[0])
+            self.rstats = DevBuf(engine, 32)
+            self.rstats.zero()
         if heads:  # the blob reader's host pass, then 48 bytes per blob in HBM (kd_geom_filter_heads)
             import time
 
@@ -554,6 +574,7 @@ class FilterPipeline:
                                             self._fe, flags, self.bits, self.match.ptr, self.keep.ptr,
                                             ctypes.cast(self.n_keep.ptr, N.c_u64p), self.enc.ptr if self.enc else None,
                                             self.enc_ok.ptr if self.enc_ok else None), "kd_geom_filter_deltas")
+            self._refine(ho, no, hn, nn, flags & N.KD_GF_DELTA_HEADS)
             return
         if self.heads is not None:
             (ho, no), (hn, nn) = self.heads
@@ -564,12 +585,31 @@ class FilterPipeline:
                                            ctypes.cast(self.n_keep.ptr, N.c_u64p), self.enc.ptr if self.enc else None,
                                            self.enc_ok.ptr if self.enc_ok else None, N.KD_MEM_DEVICE),
                     "kd_geom_filter_heads")
+            self._refine(ho, no, hn, nn, 0)
             return
         N.check(L.kd_geom_filter(ctx, ctypes.byref(self._ob), ctypes.byref(self._nb), self.delta.ptr, self.cap,
                                  ctypes.cast(self.counts.ptr + 24, N.c_u64p), N.KD_MEM_DEVICE, ctypes.byref(self._kc),
                                  self._fe, self.flags, self.bits, self.match.ptr, self.keep.ptr,
                                  ctypes.cast(self.n_keep.ptr, N.c_u64p), self.enc.ptr if self.enc else None,
                                  self.enc_ok.ptr if self.enc_ok else None, N.KD_MEM_DEVICE), "kd_geom_filter")
+
+    def _refine(self, ho, no, hn, nn, flags):
+        """the exact stage over the step's candidates (polygons given): codes, keep and n_keep in place"""
+        if self._poly is None:
+            return
+        L, ctx = self.eng.L, self.eng.ctx
+        N.check(L.kd_geom_refine(ctx, ctypes.byref(self._poly), ho.ptr, no, hn.ptr, nn, N.KD_MEM_DEVICE,
+                                 ctypes.byref(self._ob), ctypes.byref(self._nb), self.delta.ptr, self.cap,
+                                 self.counts.ptr + 24, N.KD_MEM_DEVICE, flags, self.match.ptr, self.keep.ptr,
+                                 self.n_keep.ptr, self.rstats.ptr, N.KD_MEM_DEVICE), "kd_geom_refine")
+
+    def refine_stats(self):
+        """the last step's kd_geom_refine counters: candidate sides decided true / false, left
+        undecided, unsupported or malformed (None without polygons)"""
+        if self._poly is None:
+            return None
+        st = self.rstats.download(np.uint64, 4)
+        return {"true": int(st[0]), "false": int(st[1]), "undecided": int(st[2]), "unsupported": int(st[3])}
 
     def results(self):
         """host copies: counts, delta [n, 2], codes [n, 2], keep [k], enc [n, bits/2], enc_ok [n]"""

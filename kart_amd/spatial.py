@@ -11,9 +11,15 @@
 * ``filtered_ds_feature_deltas`` <- BaseDiffWriter.filtered_ds_feature_deltas
   (kart/base_diff_writer.py:279-329): every delta's old and new geometry is found in its feature
   blob and envelope-tested on the GPU in one batch (``kd_geom_filter``), the deltas that may match
-  come back compacted in key order, and only those are resolved on the host.
+  come back compacted in key order, and only those are resolved on the host.  A filter that carries
+  its polygon rings (``from_polygons`` / ``from_wkt`` / ``from_ring``: the reference allows only
+  POLYGON and MULTIPOLYGON filters, kart/spatial_filter/__init__.py:261) and is no rectangle has its
+  candidates decided on the GPU too (``kd_geom_refine``: Intersects wherever FP64 certifies the
+  answer); what stays a candidate after that — touching configurations, unsupported WKB — follows
+  the host path as before.
 """
 import ctypes
+import re
 import struct
 from enum import Enum, auto
 
@@ -99,12 +105,16 @@ class SpatialFilter:
     geometry, the dataset's geometry column, and the exact test ``intersects(gpkg_bytes) -> bool``
     (the prepared filter geometry's Intersects; optional)."""
 
-    def __init__(self, filter_env=None, geom_column_name=None, intersects=None, rectangle=False, match_all=False):
+    def __init__(self, filter_env=None, geom_column_name=None, intersects=None, rectangle=False, match_all=False,
+                 polygons=None):
         self.match_all = match_all
         self.filter_env = None if match_all else tuple(float(x) for x in filter_env)
         self.geom_column_name = geom_column_name
         self.intersects = intersects
         self.rectangle = bool(rectangle)
+        # the filter geometry itself: [polygon][ring][(x, y)], every ring closed (None: envelope only)
+        self.polygons = _closed_polygons(polygons) if polygons is not None else None
+        self._poly_arrays = None
         self.stats = {"unverified": 0}
 
     @classmethod
@@ -117,11 +127,41 @@ class SpatialFilter:
     def from_ring(cls, ring, geom_column_name=None, intersects=None):
         """a polygon filter from its exterior ring [(x, y), ...]; a point's Intersects is tested
         exactly (point in polygon, boundary included), other geometries need ``intersects``"""
-        xs, ys = [p[0] for p in ring], [p[1] for p in ring]
+        env, rect = _ring_env_rect(ring)
+        return cls(env, geom_column_name, intersects=intersects or _ring_point_test(ring), rectangle=rect,
+                   polygons=[[ring]])
+
+    @classmethod
+    def from_polygons(cls, polygons, geom_column_name=None, intersects=None):
+        """a polygon or multipolygon filter: ``polygons`` = [polygon], polygon = [ring] (exterior
+        first, then holes), ring = [(x, y), ...] (closed here if it is not).  The filter's region is
+        the even-odd interior of all rings, boundary included.  ``rectangle`` by from_ring's rule (one
+        ring that is its own envelope's four corners)."""
+        polys = _closed_polygons(polygons)
+        pts = [p for poly in polys for ring in poly for p in ring]
+        if not pts:
+            raise ValueError("a spatial filter needs at least one ring")
+        xs, ys = [p[0] for p in pts], [p[1] for p in pts]
         env = (min(xs), max(xs), min(ys), max(ys))
-        corners = {(env[0], env[2]), (env[1], env[2]), (env[1], env[3]), (env[0], env[3])}
-        rect = len(set(ring)) == 4 and set(ring) == corners
-        return cls(env, geom_column_name, intersects=intersects or _ring_point_test(ring), rectangle=rect)
+        rect = len(polys) == 1 and len(polys[0]) == 1 and _ring_env_rect(polys[0][0])[1]
+        return cls(env, geom_column_name, intersects=intersects, rectangle=rect, polygons=polys)
+
+    @classmethod
+    def from_wkt(cls, text, geom_column_name=None, intersects=None):
+        """from POLYGON(...) / MULTIPOLYGON(...) WKT — the only types the reference accepts as a
+        spatial filter (kart/spatial_filter/__init__.py:261); Z / M ordinates are dropped"""
+        return cls.from_polygons(parse_polygon_wkt(text), geom_column_name, intersects)
+
+    def polygon_arrays(self):
+        """(xy float64 [n_vert, 2], ring_off uint64 [n_ring + 1]) of the filter's rings — kd_filter_poly;
+        built once, so that the native side recognises the same filter by its address"""
+        if self._poly_arrays is None:
+            rings = [r for poly in self.polygons for r in poly]
+            xy = np.ascontiguousarray(np.array([p for r in rings for p in r], np.float64).reshape(-1, 2))
+            off = np.zeros(len(rings) + 1, np.uint64)
+            off[1:] = np.cumsum([len(r) for r in rings])
+            self._poly_arrays = (xy, off)
+        return self._poly_arrays
 
     def for_schema(self, schema):
         """transform_for_schema_and_crs (identity CRS): the dataset's first geometry column; a schema
@@ -132,6 +172,9 @@ class SpatialFilter:
         if not cols:
             return SpatialFilter.MATCH_ALL
         out = SpatialFilter(self.filter_env, cols[0].name, self.intersects, self.rectangle)
+        out.polygons = self.polygons
+        if self.polygons is not None:
+            out._poly_arrays = self.polygon_arrays()
         out.stats = self.stats
         return out
 
@@ -185,6 +228,80 @@ class SpatialFilter:
 
 
 SpatialFilter.MATCH_ALL = SpatialFilter(match_all=True)
+
+
+def _ring_env_rect(ring):
+    """(envelope, is the ring exactly its envelope's four corners?) of a ring"""
+    ring = [tuple(p) for p in ring]
+    xs, ys = [p[0] for p in ring], [p[1] for p in ring]
+    env = (min(xs), max(xs), min(ys), max(ys))
+    corners = {(env[0], env[2]), (env[1], env[2]), (env[1], env[3]), (env[0], env[3])}
+    return env, len(set(ring)) == 4 and set(ring) == corners
+
+
+def _closed_polygons(polygons):
+    """[polygon][ring][(float x, float y)] with every ring closed; empty rings and polygons dropped"""
+    out = []
+    for poly in polygons:
+        rings = []
+        for ring in poly:
+            r = [(float(p[0]), float(p[1])) for p in ring]
+            if not r:
+                continue
+            if r[0] != r[-1]:
+                r.append(r[0])
+            if len(r) < 4:
+                raise ValueError("a polygon ring needs at least three vertices")
+            if any(c != c or c in (float("inf"), float("-inf")) for p in r for c in p):
+                raise ValueError("a spatial filter's vertices must be finite")
+            rings.append(r)
+        if rings:
+            out.append(rings)
+    return out
+
+
+_WKT_NUM = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?"
+
+
+def parse_polygon_wkt(text):
+    """[polygon][ring][(x, y)] of POLYGON / MULTIPOLYGON WKT (an optional SRID=n; prefix and Z / M / ZM
+    tags accepted, extra ordinates dropped); ValueError for anything else, EMPTY included"""
+    t = text.strip()
+    m = re.match(r"(?is)^(?:SRID=\d+;)?\s*(MULTIPOLYGON|POLYGON)\s*(?:ZM|Z|M)?\s*(\(.*\))\s*$", t)
+    if not m:
+        raise ValueError("a spatial filter must be POLYGON or MULTIPOLYGON WKT, not %r" % t[:40])
+    kind, body = m.group(1).upper(), m.group(2)
+    if not re.fullmatch(r"[\s(),0-9eE.+-]*", body):
+        raise ValueError("malformed WKT")
+    depth, start, rings_at = 0, None, 2 if kind == "POLYGON" else 3
+    polys, cur = [], None
+    for i, ch in enumerate(body):
+        if ch == "(":
+            depth += 1
+            if depth == rings_at - 1:
+                cur = []
+            elif depth == rings_at:
+                start = i + 1
+            elif depth > rings_at:
+                raise ValueError("malformed WKT")
+        elif ch == ")":
+            if depth == rings_at:
+                ring = []
+                for c in body[start:i].split(","):
+                    nums = re.findall(_WKT_NUM, c)
+                    if len(nums) < 2 or len(nums) > 4:
+                        raise ValueError("malformed WKT coordinate %r" % c.strip())
+                    ring.append((float(nums[0]), float(nums[1])))
+                cur.append(ring)
+            elif depth == rings_at - 1:
+                polys.append(cur)
+                cur = None
+            depth -= 1
+            if depth < 0:
+                raise ValueError("malformed WKT")
+    if depth != 0 or not polys:
+        raise ValueError("malformed WKT")
+    return polys
 
 
 def _ring_point_test(ring):
@@ -328,6 +445,44 @@ def geom_filter_heads(engine, old_heads, new_heads, pairs, filt_env, rectangle=F
     return match[:n], keep[:k], (enc[:n] if bits else None), (ok[:n] if bits else None)
 
 
+def geom_refine(engine, polygon_arrays, old_heads, new_heads, pairs, codes, arenas, delta_heads=False):
+    """kd_geom_refine over host buffers: the sides ``codes`` has as 1 (CANDIDATE) decided against the
+    filter polygon where FP64 certifies Intersects.  ``polygon_arrays`` = (xy [n_vert, 2], ring_off
+    [n_ring + 1]) (SpatialFilter.polygon_arrays); heads, pairs, ``arenas`` ((od, oo), (nd, no)) and
+    ``delta_heads`` as in geom_filter_heads.  Returns (codes uint8 [n, 2], keep uint32 [k], stats):
+    stats = candidate sides decided true / false, left undecided, unsupported or malformed."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    n = pairs.shape[0]
+    xy = np.ascontiguousarray(polygon_arrays[0], np.float64).reshape(-1, 2)
+    roff = np.ascontiguousarray(polygon_arrays[1], np.uint64)
+    fp = N.KdFilterPoly()
+    fp.xy = N.ptr(xy)
+    fp.ring_off = N.ptr(roff)
+    fp.n_ring = int(roff.shape[0]) - 1
+    fp.n_vert = int(xy.shape[0])
+    hs = [np.ascontiguousarray(h, GEOM_HEAD) for h in (old_heads, new_heads)]
+    blobs = []
+    for d, o in arenas:
+        b = N.KdBlobs()
+        b.n = int(o.shape[0]) - 1
+        b.data = N.ptr(d) if d.size else N.ptr(_PAD)
+        b.off = N.ptr(o)
+        b.mem = N.KD_MEM_HOST
+        blobs.append(b)
+    match = np.zeros((max(n, 1), 2), np.uint8)
+    match[:n] = np.asarray(codes, np.uint8).reshape(n, 2)
+    keep = np.zeros(max(n, 1), np.uint32)
+    nk = ctypes.c_uint64()
+    st = np.zeros(4, np.uint64)
+    N.check(engine.L.kd_geom_refine(
+        engine.ctx, ctypes.byref(fp), hs[0].ctypes.data if hs[0].size else None, hs[0].shape[0],
+        hs[1].ctypes.data if hs[1].size else None, hs[1].shape[0], N.KD_MEM_HOST, ctypes.byref(blobs[0]),
+        ctypes.byref(blobs[1]), N.ptr(pairs), n, None, N.KD_MEM_HOST, N.KD_GF_DELTA_HEADS if delta_heads else 0,
+        N.ptr(match), N.ptr(keep), ctypes.byref(nk), N.ptr(st), N.KD_MEM_HOST), "kd_geom_refine")
+    stats = {"true": int(st[0]), "false": int(st[1]), "undecided": int(st[2]), "unsupported": int(st[3])}
+    return match[:n], keep[:int(nk.value)], stats
+
+
 def _blob_of(kv):
     """the LazyBlob behind a delta half's lazy value (Delta.old / .new), or None"""
     if kv is None:
@@ -392,6 +547,15 @@ def filtered_ds_feature_deltas(engine, ds_diff, old_version, new_version, spatia
         d[pres] = h[pairs[pres, s].astype(np.int64)]
         dense.append(d)
     codes, keep, _, _ = geom_filter_heads(engine, dense[0], dense[1], pairs, env, rect, delta_heads=True)
+    psf = old_sf if not old_sf.match_all else new_sf
+    if psf.polygons and not rect:
+        # the exact stage: candidates decided against the filter's rings on the GPU; what it cannot
+        # certify (touching configurations, unsupported WKB) stays a candidate for _resolve
+        codes, keep, rst = geom_refine(engine, psf.polygon_arrays(), dense[0], dense[1], pairs, codes, sides,
+                                       delta_heads=True)
+        acc = spatial_filter.stats.setdefault("refine", {})
+        for k, v in rst.items():
+            acc[k] = acc.get(k, 0) + v
     kept = np.zeros(n, bool)
     kept[keep] = True
     for i, (key, d) in enumerate(items):
