@@ -215,7 +215,10 @@ int kd_diff2_device_ex(kd_ctx* ctx, const kd_side* base, const kd_side* target, 
  * (pu = the (base, target) update pairs, or NULL: blob u on both sides).  masks[u*words + w]
  * bit k set iff union key k changed under Python `==`.  status[u]: 0 ok, 1 malformed blob,
  * 2 unknown legend, 3 too many values, 4 unsupported value (nested container, invalid ext 'G'):
- * nonzero -> the caller recomputes that update on the CPU path.
+ * nonzero -> the caller recomputes that update on the CPU path.  masks[u] is all zero wherever
+ * status[u] != 0, whatever was found before the failure.  A compared key whose value index lies
+ * at or beyond the blob's value count gives status 1 (after status 4: a malformed value or
+ * trailing bytes win).
  * pairs_mem / out_mem say where pu and masks/status live.  Device form: with d_n_upd != NULL the
  * update count is read from that device counter (no host sync between classify and diff), pu
  * and the outputs must be device memory, and n_upd is the capacity — an upper bound of *d_n_upd

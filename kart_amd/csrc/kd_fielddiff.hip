@@ -210,7 +210,7 @@ struct FdTabT {
     typename ASP<AS, i16>::type map_o;       // [n_lo*n_keys]
     typename ASP<AS, i16>::type map_n;       // [n_ln*n_keys]
     typename ASP<AS, u64>::type cmp;         // [words]
-    typename ASP<AS, u8>::type aligned;      // [n_lo*n_ln]: maps identical on every compared key
+    typename ASP<AS, u16>::type aligned;     // [n_lo*n_ln]: 0, or (maps identical on every compared key) 1 + the values those keys need
     typename ASP<AS, i16>::type key_of_val;  // [n_lo*maxv]: union key of value v of legend lo (-1 none)
 };
 typedef FdTabT<-1> FdTab;
@@ -294,8 +294,10 @@ __device__ __forceinline__ u8 diff_one(P ob, u32 on, P nb, u32 nn, const TB& tb,
     const int li_n = find_legend(tb.leg_n, tb.n_ln, nb + lpn);
     if (li_o < 0 || li_n < 0) return 2;
     if (cvo > FD_MAXV || cvn > FD_MAXV) return 3;
-    const bool al = tb.aligned[li_o * tb.n_ln + li_n];
-    if (al && cvo == cvn) {
+    // lockstep when the maps agree and every compared key's value is there (a blob short of them
+    // takes the general path, which finds the missing value: status 1 behind status 4)
+    const u32 al = tb.aligned[li_o * tb.n_ln + li_n];
+    if (al && cvo == cvn && cvo + 1 >= al) {
         const auto kov = tb.key_of_val + (u64)li_o * tb.maxv;
         u32 pa = po, pb = pn;
         for (u32 v = 0; v < cvo; v++) {
@@ -1015,9 +1017,11 @@ __device__ __forceinline__ u8 diff_body(const BL& A, const BL& B, const TB& tb, 
                                         int li_o, int li_n, u64 mk[4], u64* m, const FdQueue& q) {
     if (li_o < 0 || li_n < 0) return 2;
     if (cvo > FD_MAXV || cvn > FD_MAXV) return 3;
-    const bool al = tb.aligned[li_o * tb.n_ln + li_n];
-    if (al && cvo == cvn) {
-        // ---- lockstep: value v of both blobs belongs to the same union key ----
+    const u32 al = tb.aligned[li_o * tb.n_ln + li_n];
+    if (al && cvo == cvn && cvo + 1 >= al) {
+        // ---- lockstep: value v of both blobs belongs to the same union key, and every compared
+        //      key's value is there (a blob short of them takes the general path below, which
+        //      finds the missing value: status 1 behind status 4) ----
         const auto kov = tb.key_of_val + (u64)li_o * tb.maxv;
         u32 pa = po, pb = pn;
         for (u32 v = 0; v < cvo; v++) {
@@ -1314,7 +1318,7 @@ __global__ __launch_bounds__(FD_NT) KD_FD_ATTR void k_fielddiff(const u8* __rest
     tb.map_o = (typename ASP<3, i16>::type)(lt + to.map_o);
     tb.map_n = (typename ASP<3, i16>::type)(lt + to.map_n);
     tb.cmp = (typename ASP<3, u64>::type)(lt + to.cmp);
-    tb.aligned = (typename ASP<3, u8>::type)(lt + to.aligned);
+    tb.aligned = (typename ASP<3, u16>::type)(lt + to.aligned);
     tb.key_of_val = (typename ASP<3, i16>::type)(lt + to.key_of_val);
     const FdQueue queue{(lds_u64p)s_task, (lds_u32p)&s_ntask, TCAP};
     const u32 img0 = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_img;
@@ -1549,7 +1553,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_s(const u8* __restrict__ od
     tb.map_o = (typename ASP<3, i16>::type)(lt + to.map_o);
     tb.map_n = (typename ASP<3, i16>::type)(lt + to.map_n);
     tb.cmp = (typename ASP<3, u64>::type)(lt + to.cmp);
-    tb.aligned = (typename ASP<3, u8>::type)(lt + to.aligned);
+    tb.aligned = (typename ASP<3, u16>::type)(lt + to.aligned);
     tb.key_of_val = (typename ASP<3, i16>::type)(lt + to.key_of_val);
     const FdQueue none{(lds_u64p) nullptr, (lds_u32p)&s_dummy, 0};  // payloads compare in place
     const u32 img_o = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_img;
@@ -1726,7 +1730,7 @@ __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WP
     tb.map_o = (typename ASP<3, i16>::type)(lt + to.map_o);
     tb.map_n = (typename ASP<3, i16>::type)(lt + to.map_n);
     tb.cmp = (typename ASP<3, u64>::type)(lt + to.cmp);
-    tb.aligned = (typename ASP<3, u8>::type)(lt + to.aligned);
+    tb.aligned = (typename ASP<3, u16>::type)(lt + to.aligned);
     tb.key_of_val = (typename ASP<3, i16>::type)(lt + to.key_of_val);
     const FdQueue queue{(lds_u64p)s_task, (lds_u32p)&s_ntask, TCAP};
     uint2 pr_n = load_pair(u1 + lane);
@@ -1846,7 +1850,14 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
             if (s >= 0 && (u32)s + 1 > nvo[l]) nvo[l] = (u32)s + 1;
         }
     for (int l = 0; l < nlo; l++) maxv = std::max<int>(maxv, (int)nvo[l]);
-    std::vector<u8> aligned((size_t)nlo * nln, 0);
+    std::vector<u32> need(nlo, 0);  // per old legend: 1 + the largest value index of a compared key
+    for (int l = 0; l < nlo; l++)
+        for (int k = 0; k < nk; k++) {
+            if (!((mp->cmp_mask[k >> 6] >> (k & 63)) & 1)) continue;
+            int s = mp->map_old[(size_t)l * nk + k];
+            if (s >= 0 && (u32)s + 1 > need[l]) need[l] = (u32)s + 1;
+        }
+    std::vector<u16> aligned((size_t)nlo * nln, 0);  // 0, or 1 + need[old legend]
     for (int a = 0; a < nlo; a++)
         for (int b = 0; b < nln; b++) {
             bool ok = true;
@@ -1857,7 +1868,7 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
                 // (absent from a schema) always compares changed, so it forces the general path
                 ok = so == sn && so != -1;
             }
-            aligned[(size_t)a * nln + b] = ok ? 1 : 0;
+            aligned[(size_t)a * nln + b] = ok ? (u16)(1 + need[a]) : 0;
         }
     std::vector<i16> kov((size_t)nlo * maxv, -1);
     for (int l = 0; l < nlo; l++)
@@ -1870,7 +1881,7 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
     auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
     size_t o_lo = 0, o_ln = al(o_lo + (size_t)nlo * 40), o_mo = al(o_ln + (size_t)nln * 40),
            o_mn = al(o_mo + (size_t)nlo * nk * 2), o_cmp = al(o_mn + (size_t)nln * nk * 2),
-           o_al = al(o_cmp + (size_t)W * 8), o_kov = al(o_al + aligned.size()), o_nv = al(o_kov + kov.size() * 2),
+           o_al = al(o_cmp + (size_t)W * 8), o_kov = al(o_al + aligned.size() * 2), o_nv = al(o_kov + kov.size() * 2),
            o_end = al(o_nv + (size_t)nlo * 4);
     std::vector<u8> h(o_end, 0);
     std::memcpy(&h[o_lo], mp->leg_old_hex, (size_t)nlo * 40);
@@ -1878,7 +1889,7 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
     std::memcpy(&h[o_mo], mp->map_old, (size_t)nlo * nk * 2);
     std::memcpy(&h[o_mn], mp->map_new, (size_t)nln * nk * 2);
     std::memcpy(&h[o_cmp], mp->cmp_mask, (size_t)W * 8);
-    std::memcpy(&h[o_al], aligned.data(), aligned.size());
+    std::memcpy(&h[o_al], aligned.data(), aligned.size() * 2);
     if (!kov.empty()) std::memcpy(&h[o_kov], kov.data(), kov.size() * 2);
     std::memcpy(&h[o_nv], nvo.data(), (size_t)nlo * 4);
     void* dt;
@@ -1892,7 +1903,7 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
     const u8* base = (const u8*)dt;
     tb.leg_o = (const u32*)(base + o_lo); tb.leg_n = (const u32*)(base + o_ln);
     tb.map_o = (const i16*)(base + o_mo); tb.map_n = (const i16*)(base + o_mn);
-    tb.cmp = (const u64*)(base + o_cmp); tb.aligned = base + o_al;
+    tb.cmp = (const u64*)(base + o_cmp); tb.aligned = (const u16*)(base + o_al);
     tb.key_of_val = (const i16*)(base + o_kov);
 
     // ---- inputs ----

@@ -236,9 +236,10 @@ class Engine:
                                          min(lo), max(hi), d_pk.ptr, d_perm.ptr), "kd_delta_pk_order")
         return d_pk.download(np.int64, n), d_perm.download(np.uint32, n)
 
-    def fielddiff(self, old_data, old_off, new_data, new_off, pairs, maps):
+    def fielddiff(self, old_data, old_off, new_data, new_off, pairs, maps, size_hint=0):
         """Blob arenas (uint8 data, uint64 off[n+1]) per side; pairs uint32 [n, 2] (old blob,
-        new blob) or None (blob u on both sides); maps: schema.FieldMaps.
+        new blob) or None (blob u on both sides); maps: schema.FieldMaps; size_hint: the typical
+        blob size in bytes (kd_blobs.size_hint; 0 = the arenas' mean), which picks the window shape.
         Returns (masks uint64 [n, words], status uint8 [n])."""
         old_data = np.ascontiguousarray(old_data, np.uint8)
         new_data = np.ascontiguousarray(new_data, np.uint8)
@@ -253,6 +254,7 @@ class Engine:
             b.data = N.ptr(d) if d.size else N.ptr(_PAD)
             b.off = N.ptr(o)
             b.mem = N.KD_MEM_HOST
+            b.size_hint = int(size_hint)
         masks = np.zeros((max(n, 1), maps.words), np.uint64)
         status = np.zeros(max(n, 1), np.uint8)
         km = maps.kd_maps()

@@ -426,7 +426,8 @@ static int parse_header(const uint8_t* b, uint32_t n, const uint8_t** legend_hex
  *   old blob of update u = old_data[old_off[oi]:old_off[oi+1]], oi = old_idx ? old_idx[u] : u
  *   legends: n_leg 40-byte hex strings per side; maps: [n_leg][n_keys] int16 source codes
  *   cmp_mask: [words] keys to compare (keys starting "__" are excluded by the host)
- *   status[u]: 0 ok, 1 malformed blob, 2 unknown legend, 3 too many values, 4 unsupported value
+ *   status[u]: 0 ok, 1 malformed blob, 2 unknown legend, 3 too many values, 4 unsupported value;
+ *   masks[u] is all zero wherever status[u] != 0
  * Returns 0. */
 int kdo_fielddiff(uint64_t n_upd,
                   const uint8_t* old_data, const uint64_t* old_off, const uint32_t* old_idx,
@@ -483,6 +484,8 @@ int kdo_fielddiff(uint64_t n_upd,
             }
             if (changed) m[k >> 6] |= 1ull << (k & 63);
         }
+        /* a failure found while resolving the keys: no mask bit of a failed update stays set */
+        if (status[u]) for (int w = 0; w < words; w++) m[w] = 0;
     }
     return 0;
 }
