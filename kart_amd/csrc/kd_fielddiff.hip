@@ -11,20 +11,30 @@
 // bool == int, exact int/float compare, IEEE float ==, str/bytes by payload, bin == ext 'G'
 // payload, None only == None, empty ext 'G' -> None.
 //
-// k_fielddiff (one wave per workgroup, UPR updates per round, one lane per update):
+// k_fielddiff<shape, MR> — the windowed kernel, the default for tables that fit LDS (up to 16 KiB
+// packed).  One wave per workgroup, UPR updates per round, one lane per update, rounds grid-stride.
 //   1. LDS windows.  Per blob only a head window (NH 16-B chunks from the blob's aligned start) and a
-//      tail window (the NTL aligned chunks ending with the blob's last byte) are
-//      copied to LDS by LDS-DMA — the msgpack headers, the legend, and the short values that follow
-//      a long one.  Long payloads (geometries) never enter LDS: 17.3 KiB per 52-update round.
-//   2. Parse: each lane walks its two blobs value by value from the windows (table-driven header
-//      decode from a 12-byte window; bytes outside both windows come from global memory), compares
-//      scalars and short payloads in registers or LDS, and queues every byte payload it cannot see
-//      whole in LDS as a compare task (old address, new address, length, lane, key).
-//   3. Tasks: the wave compares the queued payloads cooperatively, 16 lanes x 16 B per step straight
-//      from HBM (coalesced; the new side realigned to the old side's byte offset with a funnel
-//      shift), and ORs the changed keys into the owners' masks in LDS.
-// Payloads of unequal length are "changed" without reading them.  Tables too large for LDS take
-// k_fielddiff_g (one lane per update, everything from global memory).
+//      tail window (the NTL aligned chunks ending with the blob's last byte) are copied to LDS by
+//      LDS-DMA — the msgpack headers, the legend, and the short values that follow a long one.  Long
+//      payloads (geometries) never enter LDS.  The next round's windows are staged while this
+//      round's queued payloads are compared: one HBM round trip per round.
+//   2. Parse: each lane walks its two blobs value by value from the windows (header and legend of
+//      the canonical form in one batch, then a table-driven decode from a 12-byte window; bytes
+//      outside both windows come from global memory), compares scalars and short payloads in
+//      registers or LDS, and queues every byte payload it cannot see whole in LDS as a compare task
+//      (old address, new address, length, lane, key).
+//   3. Tasks: the wave compares the queued payloads cooperatively, TG lanes x 16 B per step and TM
+//      payloads per group per pass, straight from HBM with byte-addressed loads (nothing realigned
+//      or masked), and ORs the changed keys into the owners' masks in LDS.
+//   Four instantiations: the shape S (32 updates, 8 + 3 chunks: small features fit the head window
+//   whole) or L (64 updates, 5 + 4 chunks) by the typical blob size, and MR = 1 or 4 mask words in
+//   registers by the union key count.
+// k_fielddiff_g — tables too large for LDS: one lane per update, everything from global memory
+// through the generic decoder.
+// k_fielddiff_s (fd_stream=1) and k_fdwalk (fd_walk=1) — measured alternatives that no default
+// selects; they share the windowed decoder through the blob types SBlobT / HBlobT.
+// Payloads of unequal length are "changed" without reading them.  Every kernel takes the update
+// count from the host, from a device word, or from the join's partial counters (fd_dev_count).
 #include <cstdlib>
 #include <type_traits>
 
@@ -459,23 +469,9 @@ __device__ __forceinline__ u32 lds_u32(u32 addr) { return *(lp32)(size_t)addr; }
 
 // bytes [p, p + 12) of a blob as three little-endian words (bytes past the blob: zero or garbage;
 // callers bound every access by the blob length)
-#ifndef KD_FD_LDSU
-#define KD_FD_LDSU 0  // 1: LDS windows read by byte-addressed ds_read_b128 (measured ~2 % slower than aligned dwords + v_alignbyte)
-#endif
-typedef const __attribute__((address_space(3))) u32x4_b* lp128b;
-__device__ __forceinline__ u32x4 lds_u128(u32 addr) { return *(lp128b)(size_t)addr; }
-
 template <class BL>
 __device__ __forceinline__ void rd12(const BL& b, u32 p, u32& x0, u32& x1, u32& x2) {
     const u32 x = p + b.s0, x4 = x & ~3u, s = x & 3;
-    if (KD_FD_LDSU) {  // one 16-B read at the byte address (the 4 bytes past the 12 are not used)
-        const u32 o = b.win(x, 12);
-        if (BL::lds_only || o != ~0u) {
-            const u32x4 v = lds_u128(b.img + o);
-            x0 = v.x; x1 = v.y; x2 = v.z;
-            return;
-        }
-    }
     u32 w0, w1, w2, w3;
     const u32 o = b.win(x4, 16);
     if (BL::lds_only || o != ~0u) {
@@ -514,16 +510,6 @@ __device__ __forceinline__ void rd_legend(const HBlobT<GUARD>& b, u32 lp, u32 h[
 template <class BL>
 __device__ __forceinline__ void rd_legend(const BL& b, u32 lp, u32 h[10]) {
     const u32 x = lp + b.s0, x4 = x & ~3u, s = x & 3;
-    if (KD_FD_LDSU) {
-        const u32 o = b.win(x, 40);
-        if (BL::lds_only || o != ~0u) {
-            const u32x4 c0 = lds_u128(b.img + o), c1 = lds_u128(b.img + o + 16), c2 = lds_u128(b.img + o + 32);
-            h[0] = c0.x; h[1] = c0.y; h[2] = c0.z; h[3] = c0.w;
-            h[4] = c1.x; h[5] = c1.y; h[6] = c1.z; h[7] = c1.w;
-            h[8] = c2.x; h[9] = c2.y;
-            return;
-        }
-    }
     u32 w[11];
     const u32 o = b.win(x4, 44);
     if (BL::lds_only || o != ~0u) {
@@ -602,7 +588,7 @@ __device__ __forceinline__ u32 scalar_eq(const WVal& a, const WVal& b) {
     return a.len == 0 ? 0u : 2u;
 }
 
-// LDS byte compare: 32-byte blocks, the 9 aligned words of each side read together and realigned
+// LDS byte compare: 16-byte blocks, the 5 aligned words of each side read together and realigned
 // with v_alignbyte; bytes past n masked (the aligned reads may run up to 4 bytes past either range,
 // still inside the block's LDS, or return 0 past its end)
 __device__ bool lds_bytes_eq(u32 a, u32 b, u32 n) {
@@ -622,22 +608,6 @@ __device__ bool lds_bytes_eq(u32 a, u32 b, u32 n) {
         wa += 16;
         wb += 16;
         rem = rem > 16 ? rem - 16 : 0;
-    }
-    return diff == 0;
-}
-
-// LDS byte compare by byte-addressed 16-B reads (the reads may run up to 15 bytes past either range,
-// inside the block's LDS, or return 0 past its end; bytes past n are masked)
-__device__ bool lds_bytes_eq_u(u32 a, u32 b, u32 n) {
-    u32 diff = 0;
-    for (u32 o = 0; o < n && diff == 0; o += 16) {
-        const u32x4 x = lds_u128(a + o) ^ lds_u128(b + o);
-        const u32 r = n - o;
-        const u32 m0 = r >= 4 ? ~0u : (1u << (8 * r)) - 1;
-        const u32 m1 = r >= 8 ? ~0u : r <= 4 ? 0u : (1u << (8 * (r - 4))) - 1;
-        const u32 m2 = r >= 12 ? ~0u : r <= 8 ? 0u : (1u << (8 * (r - 8))) - 1;
-        const u32 m3 = r >= 16 ? ~0u : r <= 12 ? 0u : (1u << (8 * (r - 12))) - 1;
-        diff = (x.x & m0) | (x.y & m1) | (x.z & m2) | (x.w & m3);
     }
     return diff == 0;
 }
@@ -671,10 +641,6 @@ __device__ bool glb_bytes_eq(u64 a, u64 b, u32 n) {
 #define KD_FD_PROBE_NOLDSCMP 0  // timing probe only (results invalid): in-LDS payload compares skipped
 #endif
 
-#ifndef KD_FD_HEADF
-#define KD_FD_HEADF 1  // windowed kernel: the fast header read (head_fast) before the general parse
-#endif
-
 // Per-round queue of payloads compared cooperatively after the parse (in LDS).
 typedef __attribute__((address_space(3))) u64* lds_u64p;
 typedef __attribute__((address_space(3))) u32* lds_u32p;
@@ -701,18 +667,10 @@ __device__ __forceinline__ bool task_put(const FdQueue& q, u64 a, u64 b, u32 n, 
 template <class BL>
 __device__ __forceinline__ u32 range_eq(const BL& A, u32 pa, const BL& B, u32 pb, u32 n, int key, const FdQueue& q) {
     const u32 ya = pa + A.s0, yb = pb + B.s0;  // offsets from the head bases
-    if (KD_FD_LDSU) {
-        const u32 oa = A.win(ya, n), ob = B.win(yb, n);
-        if (BL::lds_only || (oa != ~0u && ob != ~0u)) {
-            if (KD_FD_PROBE_NOLDSCMP) return 0u;
-            return lds_bytes_eq_u(A.img + oa, B.img + ob, n) ? 0u : 1u;
-        }
-    } else {
-        const u32 oa = A.win(ya & ~3u, n + 8), ob = B.win(yb & ~3u, n + 8);
-        if (BL::lds_only || (oa != ~0u && ob != ~0u)) {
-            if (KD_FD_PROBE_NOLDSCMP) return 0u;
-            return lds_bytes_eq(A.img + oa + (ya & 3), B.img + ob + (yb & 3), n) ? 0u : 1u;
-        }
+    const u32 oa = A.win(ya & ~3u, n + 8), ob = B.win(yb & ~3u, n + 8);
+    if (BL::lds_only || (oa != ~0u && ob != ~0u)) {
+        if (KD_FD_PROBE_NOLDSCMP) return 0u;
+        return lds_bytes_eq(A.img + oa + (ya & 3), B.img + ob + (yb & 3), n) ? 0u : 1u;
     }
     const u64 xa = A.start + pa, xb = B.start + pb;
     if (task_put(q, xa, xb, n, key)) return 3;
@@ -1087,78 +1045,6 @@ __device__ __forceinline__ u8 diff_body(const BL& A, const BL& B, const TB& tb, 
     return 0;
 }
 
-// Cooperative compare of M queued payloads by one 16-lane group: lane j of step s takes old chunk
-// c = 16 s + j of each payload's aligned range and the matching 16 new bytes (two aligned chunks,
-// funnel-shifted by the two sides' relative skew), every payload's loads issued before any compare.
-// d[m] = "payload m differs", on every lane of the group.  A chunk is loaded only if it holds a
-// byte of its payload (else zeros); an absent payload has n = 0.
-template <int M, int G, int S>
-__device__ __forceinline__ void coop_differs(const u64 (&a)[M], const u64 (&b)[M], const u32 (&n)[M], bool (&d)[M]) {
-    const u32 j = threadIdx.x & (G - 1), grp = (threadIdx.x & 63) / G;
-    u32 sa[M], sd[M], nch[M];
-    u64 abase[M], ebase[M];
-    u32 nmax = 0;
-    bool diff[M];
-#pragma unroll
-    for (int m = 0; m < M; m++) {
-        sa[m] = (u32)(a[m] & 15);
-        abase[m] = a[m] - sa[m];
-        const u64 e = b[m] - sa[m];
-        ebase[m] = e & ~(u64)15;
-        sd[m] = (u32)(e & 15);
-        nch[m] = n[m] ? (n[m] + sa[m] + 15) >> 4 : 0;
-        nmax = nch[m] > nmax ? nch[m] : nmax;
-        diff[m] = false;
-    }
-    for (u32 c0 = 0; c0 < nmax; c0 += G * S) {
-        u32x4 O[M][S], N0[M][S], N1[M][S];
-#pragma unroll
-        for (int m = 0; m < M; m++)
-#pragma unroll
-            for (int s = 0; s < S; s++) {
-                const u32 c = c0 + G * s + j;
-                const bool act = c < nch[m];
-                const u64 oa = abase[m] + 16ull * c, na = ebase[m] + 16ull * c, bend = b[m] + n[m];
-                const bool ok0 = act && na < bend && na + 16 > b[m];
-                const bool ok1 = act && sd[m] != 0 && na + 16 < bend;
-                const u32x4 z = {0, 0, 0, 0};
-                O[m][s] = act ? *(gp128)oa : z;
-                N0[m][s] = ok0 ? *(gp128)na : z;
-                N1[m][s] = ok1 ? *(gp128)(na + 16) : z;
-            }
-#pragma unroll
-        for (int m = 0; m < M; m++)
-#pragma unroll
-            for (int s = 0; s < S; s++) {
-                const u32 c = c0 + G * s + j;
-                const u32 q = sd[m] >> 2, sb = sd[m] & 3;
-                // dwords q .. q+4 of the 8 new dwords (two select stages on named values: an array
-                // here was turned into a dynamically indexed scratch copy)
-                const u32x4 P0 = N0[m][s], P1 = N1[m][s];
-                const bool s1 = q & 1, s2 = q & 2;
-                const u32 b0 = s1 ? P0.y : P0.x, b1 = s1 ? P0.z : P0.y, b2 = s1 ? P0.w : P0.z;
-                const u32 b3 = s1 ? P1.x : P0.w, b4 = s1 ? P1.y : P1.x, b5 = s1 ? P1.z : P1.y;
-                const u32 b6 = s1 ? P1.w : P1.z;
-                const u32 t2[5] = {s2 ? b2 : b0, s2 ? b3 : b1, s2 ? b4 : b2, s2 ? b5 : b3, s2 ? b6 : b4};
-                const u32 o[4] = {O[m][s].x, O[m][s].y, O[m][s].z, O[m][s].w};
-                // payload bytes of this chunk: t in [lo, hi)
-                const int lo = c == 0 ? (int)sa[m] : 0;
-                const int hi = (int)n[m] + (int)sa[m] - 16 * (int)c;
-                u32 dd = 0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const u32 nw = __builtin_amdgcn_alignbyte(t2[k + 1], t2[k], sb);
-                    const u32 lm = lo >= 4 * k + 4 ? 0u : lo <= 4 * k ? ~0u : ~0u << (8 * (lo - 4 * k));
-                    const u32 hm = hi <= 4 * k ? 0u : hi >= 4 * k + 4 ? ~0u : (1u << (8 * (hi - 4 * k))) - 1;
-                    dd |= (o[k] ^ nw) & lm & hm;
-                }
-                diff[m] |= c < nch[m] && dd != 0;
-            }
-    }
-#pragma unroll
-    for (int m = 0; m < M; m++) d[m] = ((__ballot(diff[m]) >> (G * grp)) & ((1ull << G) - 1)) != 0;
-}
-
 // Cooperative compare of M queued payloads by one G-lane group with byte-addressed 16-B loads (gfx950
 // runs in unaligned mode): lane j of step s compares chunk c = G s + j of both payloads at the same
 // payload offset min(16 c, n - 16) — the last chunk overlaps the one before it instead of running
@@ -1198,13 +1084,10 @@ __device__ __forceinline__ void coop_differs_u(const u64 (&a)[M], const u64 (&b)
 #pragma unroll
     for (int m = 0; m < M; m++) d[m] = ((__ballot(diff[m] != 0) >> (G * grp)) & ((1ull << G) - 1)) != 0;
 }
-#ifndef KD_FD_COOPU
-#define KD_FD_COOPU 1  // the queued payloads by byte-addressed loads (0: aligned chunks + funnel shifts)
-#endif
+// (a forwarder: called directly, coop_differs_u's load addresses in the L shape land in other registers)
 template <int M, int G, int S>
 __device__ __forceinline__ void coop_cmp(const u64 (&a)[M], const u64 (&b)[M], const u32 (&n)[M], bool (&d)[M]) {
-    if (KD_FD_COOPU) coop_differs_u<M, G, S>(a, b, n, d);
-    else coop_differs<M, G, S>(a, b, n, d);
+    coop_differs_u<M, G, S>(a, b, n, d);
 }
 
 constexpr u32 FD_TAB_LDS_MAX = 16384;
@@ -1251,13 +1134,8 @@ __device__ __forceinline__ u64 fd_dev_count(const u64* __restrict__ p, int n_par
     return (u64)hi << 32 | lo;
 }
 
-#ifdef KD_FD_WPE  // probe builds: a waves-per-SIMD floor (the register budget follows from it)
-#define KD_FD_ATTR __attribute__((amdgpu_waves_per_eu(KD_FD_WPE)))
-#else
-#define KD_FD_ATTR
-#endif
 template <int UPR, int NH, int NTL, int TM, int TG, int TS, int MR>
-__global__ __launch_bounds__(FD_NT) KD_FD_ATTR void k_fielddiff(const u8* __restrict__ od, const u64* __restrict__ ooff,
+__global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, const u64* __restrict__ ooff,
                                                      const u8* __restrict__ nd, const u64* __restrict__ noff,
                                                      const uint2* __restrict__ pairs, u64 n_upd_host,
                                                      const u64* __restrict__ n_upd_dev, int n_part, FdTab tg, FdTabOff to,
@@ -1417,7 +1295,7 @@ __global__ __launch_bounds__(FD_NT) KD_FD_ATTR void k_fielddiff(const u8* __rest
 #if KD_FD_PROBE_NOPARSE  // timing probe only (results invalid): no parse, no queued payloads
             (void)queue;
 #else
-            st = KD_FD_HEADF ? diff_one_f<MR>(A, B, tb, mk, m, queue) : diff_one_w<MR>(A, B, tb, mk, m, queue);
+            st = diff_one_f<MR>(A, B, tb, mk, m, queue);
 #endif
         }
         __syncthreads();  // parse done: the image is free, the queue complete

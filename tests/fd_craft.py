@@ -195,17 +195,23 @@ class Set:
         return O.fielddiff(*self.old_arena, *self.new_arena, None, self.maps)
 
     def table_bytes(self):
-        """size of the packed device tables (what picks k_fielddiff_g above 16 KiB): the layout of
-        fielddiff_device's one packed upload in kd_fielddiff.hip (o_lo .. o_end), restated — a change
-        of that layout has to be repeated here"""
-        al = lambda x: (x + 15) & ~15  # noqa: E731
-        m = self.maps
-        nlo, nln, nk = max(1, len(m.old_hashes)), max(1, len(m.new_hashes)), m.n_keys
-        maxv = max(1, int(m.map_old.max()) + 1)
-        t = 0
-        for part in (nlo * 40, nln * 40, nlo * nk * 2, nln * nk * 2, m.words * 8, nlo * nln * 2, nlo * maxv * 2, nlo * 4):
-            t = al(t + part)
-        return t
+        return table_bytes(self.maps)
+
+
+SMALL_TABLE, BIG_TABLE = 2048, 24 * 1024  # wide margins around the 16 KiB selector of k_fielddiff_g
+
+
+def table_bytes(m):
+    """size of the packed device tables of a FieldMaps (what picks k_fielddiff_g above 16 KiB): the
+    layout of fielddiff_device's one packed upload in kd_fielddiff.hip (o_lo .. o_end), restated — a
+    change of that layout has to be repeated here"""
+    al = lambda x: (x + 15) & ~15  # noqa: E731
+    nlo, nln, nk = max(1, len(m.old_hashes)), max(1, len(m.new_hashes)), m.n_keys
+    maxv = max(1, int(m.map_old.max()) + 1)
+    t = 0
+    for part in (nlo * 40, nln * 40, nlo * nk * 2, nln * nk * 2, m.words * 8, nlo * nln * 2, nlo * maxv * 2, nlo * 4):
+        t = al(t + part)
+    return t
 
 
 @functools.lru_cache(maxsize=None)

@@ -14,7 +14,7 @@ import pytest
 
 import fd_craft as F
 
-SMALL_TABLE, BIG_TABLE = 2048, 24 * 1024  # wide margins around the 16 KiB selector of k_fielddiff_g
+SMALL_TABLE, BIG_TABLE = F.SMALL_TABLE, F.BIG_TABLE
 
 # (name, factory, statuses that must occur, table bound)
 SETS = {

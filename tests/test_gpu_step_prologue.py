@@ -162,11 +162,23 @@ def _sides(name):
     return L.base, dataclasses.replace(L.target, oid=oid), L.base_blobs, L.target_blobs, maps, upd[keep]
 
 
-def _pipeline(engine, name, arenas=True):
+@functools.lru_cache(maxsize=None)
+def _big_maps():
+    """the layer's maps with 320 more legends that no blob names (fd_craft.bulk_legends): packed tables
+    above the 16 KiB the windowed kernels hold in LDS, so the field diff is k_fielddiff_g"""
+    import fd_craft as F
+    from kart_amd.schema import FieldMaps
+
+    L = _layer()[0]
+    legends = {**L.legends, **F.bulk_legends()}
+    return FieldMaps(L.schema, legends, L.schema, legends)
+
+
+def _pipeline(engine, name, arenas=True, big=False):
     from kart_amd.device import DiffPipeline
 
     base, target, bb, tb, maps, upd = _sides(name)
-    pipe = DiffPipeline(engine, base, target, bb, tb, maps)
+    pipe = DiffPipeline(engine, base, target, bb, tb, _big_maps() if big else maps)
     assert pipe.pk_order
     if arenas:  # update i's blobs at arena index i
         pipe.use_update_arenas(upd)
@@ -208,10 +220,10 @@ def _download(pipe):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(name, arenas):
+def _reference(name, arenas, big=False):
     """the separate calls' outputs, checked against the oracle's records (once per form, never modified)"""
     eng = _reference.engine
-    pipe = _pipeline(eng, name, arenas)
+    pipe = _pipeline(eng, name, arenas, big)
     _separate_calls(pipe, arenas)
     eng.sync()
     out = _download(pipe)
@@ -290,6 +302,29 @@ def test_gpu_step_count_pairs_form(engine, request, count, overlap):
     ref = _reference("many_tiles", False)
     _options(engine, request, step_overlap_min=0, step_count=count, step_overlap=overlap)
     pipe = _pipeline(engine, "many_tiles", arenas=False)
+    pipe.step()
+    engine.sync()
+    _assert_equal(_download(pipe), ref)
+
+
+def test_gpu_step_count_big_tables(engine, request):
+    """k_fielddiff_g, the kernel for tables too large for LDS, sums the partial counters too: many_tiles
+    (updates in more than 64 join tiles, so every one of the 64 counters holds a part of the count) under
+    maps of 24 KiB and more — every output of the step equals the separate calls run with the same maps,
+    and masks and status equal the small-table reference (legends nobody names change no result)"""
+    import fd_craft as F
+
+    small, big = _sides("many_tiles")[4], _big_maps()
+    assert F.table_bytes(small) <= 16 * 1024 and F.table_bytes(big) >= F.BIG_TABLE
+    assert big.words == small.words and big.keys == small.keys
+    tile = _layer()[3]
+    assert np.unique(tile % SLOTS).size == SLOTS
+    ref_small, ref = _reference("many_tiles", True), _reference("many_tiles", True, True)
+    assert int(ref["counts"][1]) > 1000
+    assert np.array_equal(ref["masks"], ref_small["masks"]) and np.array_equal(ref["status"], ref_small["status"])
+    _options(engine, request, step_overlap_min=0, step_count=1, step_overlap=1)
+    pipe = _pipeline(engine, "many_tiles", big=True)
+    assert pipe.masks.nbytes == ref_small["masks"].size
     pipe.step()
     engine.sync()
     _assert_equal(_download(pipe), ref)
