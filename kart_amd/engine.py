@@ -164,8 +164,8 @@ class Engine:
         c = d_c.download(np.uint64, 5)
         err = int(c[4]) & 0xFFFFFFFF
         if err:
-            raise N.Unsupported("kd_diff2: " + ("side keys not strictly ascending" if err & 1 else
-                                               "hash key collision between different filenames"))
+            raise N.Unsupported(N.KD_EUNSUPPORTED, "kd_diff2: " + ("side keys not strictly ascending" if err & 1 else
+                                                                   "hash key collision between different filenames"))
         nd, nu = int(c[3]), int(c[1])
         delta = d_delta.download(np.uint32, 2 * nd).reshape(nd, 2)
         upd = d_upd.download(np.uint32, 2 * nu).reshape(nu, 2)
@@ -184,8 +184,9 @@ class Engine:
         c = d_c.download(np.uint64, 5)
         err = int(c[4]) & 0xFFFFFFFF
         if err:
-            raise N.Unsupported("kd_merge3: err=0x%x (%s)" % (err, "keys not strictly ascending" if err & 1 else
-                                                               "hash key collision" if err & 2 else "tile overflow"))
+            raise N.Unsupported(N.KD_EUNSUPPORTED,
+                                "kd_merge3: err=0x%x (%s)" % (err, "keys not strictly ascending" if err & 1 else
+                                                              "hash key collision" if err & 2 else "tile overflow"))
         nc, nm = int(c[1]), int(c[2])
         conf = d_conf.download(np.uint32, 3 * nc).reshape(nc, 3)
         md = d_md.download(np.uint32, 2 * nm).reshape(nm, 2)
