@@ -35,6 +35,9 @@
 // selects; they share the windowed decoder through the blob types SBlobT / HBlobT.
 // Payloads of unequal length are "changed" without reading them.  Every kernel takes the update
 // count from the host, from a device word, or from the join's partial counters (fd_dev_count).
+// Shared, one definition each: fd_count (update count, pair bound), fd_load_pair / fd_load_off (an
+// update's pair and blob offsets), fd_tab_copy / fd_tab_at (the tables into LDS; their descriptor, on
+// the host too), fd_span_chunks (k_fielddiff_s); host: fd_pack_tables, FdVariant / fd_choose.
 #include <cstdlib>
 #include <type_traits>
 
@@ -1090,7 +1093,7 @@ __device__ __forceinline__ void coop_cmp(const u64 (&a)[M], const u64 (&b)[M], c
     coop_differs_u<M, G, S>(a, b, n, d);
 }
 
-constexpr u32 FD_TAB_LDS_MAX = 16384;
+constexpr u32 FD_TAB_LDS_MAX = 16384;  // tables up to this size are copied into each block's LDS
 // window shapes (updates per round, head chunks, tail chunks): small features / larger ones
 #ifndef KD_FD_SHAPE_L
 #ifndef KD_FD_TM_L
@@ -1104,8 +1107,9 @@ constexpr u32 FD_TAB_LDS_MAX = 16384;
 #ifndef KD_FD_SHAPE_S
 #define KD_FD_SHAPE_S 32, 8, 3, 1, 16, 2  // C2 (10M points): tail 2 / 3 chunks = 40.5 / 37.4 us
 #endif
-template <int UPR, int NH, int NTL, int TM, int TG, int TS>
-constexpr int fd_upr(const void*) { return UPR; }  // (the shape macros' first entry)
+#ifndef KD_FD_CAP
+#define KD_FD_CAP 12  // resident workgroups per CU at most; C2 points: 10 / 12 = 36.8 / 35.1 us (C3 is LDS-bound at 8)
+#endif
 #ifndef KD_FD_SSHAPE
 #define KD_FD_SSHAPE 32, 16384  // streamed kernel: updates per tile, LDS bytes per side
 #endif
@@ -1115,8 +1119,6 @@ constexpr int fd_upr(const void*) { return UPR; }  // (the shape macros' first e
 #ifndef KD_FD_STREAM_DEFAULT
 #define KD_FD_STREAM_DEFAULT 0
 #endif
-template <int T, int CAPB>
-constexpr int fd_stream_t() { return T; }  // tables up to this size are copied into each block's LDS
 typedef __attribute__((address_space(3))) void* fd_lds_vp;
 typedef const __attribute__((address_space(1))) void* fd_glb_vp;
 
@@ -1134,6 +1136,58 @@ __device__ __forceinline__ u64 fd_dev_count(const u64* __restrict__ p, int n_par
     return (u64)hi << 32 | lo;
 }
 
+// ---- shared by the kernels ----
+// A launch's update count n_upd (the host's, or the device's) and the bound lim below which its
+// pairs may be read: with both counts given the host's is the capacity of the pair list, so pairs
+// load before the device count has arrived.  Updates [0, end = min(lim, n_upd)) are processed.
+struct FdCount { u64 n_upd, lim, end; };
+__device__ __forceinline__ FdCount fd_count(u64 n_upd_host, const u64* __restrict__ n_upd_dev, int n_part) {
+    const bool spec = n_upd_dev && n_upd_host;
+    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
+    const u64 lim = spec ? n_upd_host : n_upd;
+    return {n_upd, lim, min(lim, n_upd)};
+}
+// update uu's (old, new) blob indices: pairs[uu] below the bound on an owner lane, else uu on both
+// sides.  (bound and owner by reference: taken by value, k_fielddiff's instruction stream changes)
+__device__ __forceinline__ uint2 fd_load_pair(const uint2* __restrict__ pairs, u64 uu, const u64& bound, const bool& owner) {
+    uint2 p = make_uint2((u32)uu, (u32)uu);
+    if (pairs && uu < bound && owner) p = pairs[uu];
+    return p;
+}
+// offsets and lengths of a pair's two blobs (zero on inactive lanes)
+__device__ __forceinline__ void fd_load_off(const u64* __restrict__ ooff, const u64* __restrict__ noff, uint2 p, bool a,
+                                            u64& os_, u64& ns_, u32& on_, u32& nn_) {
+    os_ = ns_ = 0;
+    on_ = nn_ = 0;
+    if (a) {
+        os_ = ooff[p.x];
+        ns_ = noff[p.y];
+        on_ = (u32)(ooff[p.x + 1] - os_);
+        nn_ = (u32)(noff[p.y + 1] - ns_);
+    }
+}
+
+// the packed tables into the block's dynamic LDS (16 B per lane per step), and the msgpack type table
+__device__ __forceinline__ void fd_tab_copy(u8* s_tab, const FdTabOff& to, const u8* __restrict__ tab_base) {
+    for (u32 i = 16 * threadIdx.x; i < to.bytes; i += 16 * FD_NT) *(u32x4*)(s_tab + i) = *(gp128)(tab_base + i);
+    mp_tab_to_lds();
+}
+// the tables' descriptor over a packed copy at base, with d's counts: over the device copy (AS = -1,
+// on the host) or over a block's LDS copy (AS = 3)
+template <int AS, int AD>
+__host__ __device__ __forceinline__ FdTabT<AS> fd_tab_at(typename ASP<AS, u8>::type base, const FdTabT<AD>& d, const FdTabOff& to) {
+    FdTabT<AS> tb;
+    tb.n_keys = d.n_keys; tb.words = d.words; tb.n_lo = d.n_lo; tb.n_ln = d.n_ln; tb.maxv = d.maxv;
+    tb.leg_o = (typename ASP<AS, u32>::type)(base + to.leg_o);
+    tb.leg_n = (typename ASP<AS, u32>::type)(base + to.leg_n);
+    tb.map_o = (typename ASP<AS, i16>::type)(base + to.map_o);
+    tb.map_n = (typename ASP<AS, i16>::type)(base + to.map_n);
+    tb.cmp = (typename ASP<AS, u64>::type)(base + to.cmp);
+    tb.aligned = (typename ASP<AS, u16>::type)(base + to.aligned);
+    tb.key_of_val = (typename ASP<AS, i16>::type)(base + to.key_of_val);
+    return tb;
+}
+
 template <int UPR, int NH, int NTL, int TM, int TG, int TS, int MR>
 __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, const u64* __restrict__ ooff,
                                                      const u8* __restrict__ nd, const u64* __restrict__ noff,
@@ -1146,6 +1200,8 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, 
     constexpr int NCH = (UPR * LS + 63) / 64 * 64;  // image chunks per round (whole instructions)
     constexpr u32 TCAP = UPR;          // queued payload compares per round (then a lane compares alone)
     static_assert(NTL >= 1, "window shape");
+    static_assert(UPR <= 64 && NH <= 16 && NTL <= 16,
+                  "packed fields: staging descriptors hold the owner lane in 6 bits and the window chunk in 4, task words the lane in 6");
     __shared__ u32x4 s_img[NCH];
     __shared__ u64 s_task[2 * TCAP];
     __shared__ u64 s_res[UPR];         // mask bits (keys < 64) found by the cooperative compares
@@ -1154,50 +1210,22 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, 
     using BL = WBlob<NH, NTL>;
     const int lane = threadIdx.x;
     const bool owner = lane < UPR;
-    const bool spec = n_upd_dev && n_upd_host;
-    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
-    const u64 lim = spec ? n_upd_host : n_upd;
-    const u64 end = min(lim, n_upd);
+    const FdCount cnt = fd_count(n_upd_host, n_upd_dev, n_part);
+    const u64 n_upd = cnt.n_upd, lim = cnt.lim, end = cnt.end;
     // Rounds are assigned grid-stride.  (Handing them out by an atomic counter instead, so that a
     // block made resident late takes fewer rounds, measured ~20 % slower at C3.)
     const u64 step = (u64)gridDim.x * UPR;
-    auto load_pair = [&](u64 uu) {
-        uint2 p = make_uint2((u32)uu, (u32)uu);
-        if (pairs && uu < lim && owner) p = pairs[uu];
-        return p;
-    };
-    auto load_off = [&](uint2 p, bool a, u64& os_, u64& ns_, u32& on_, u32& nn_) {
-        os_ = ns_ = 0;
-        on_ = nn_ = 0;
-        if (a) {
-            os_ = ooff[p.x];
-            ns_ = noff[p.y];
-            on_ = (u32)(ooff[p.x + 1] - os_);
-            nn_ = (u32)(noff[p.y + 1] - ns_);
-        }
-    };
     u64 u0 = (u64)blockIdx.x * UPR;
     if (u0 >= end) return;  // wave-uniform: no round for this block
     u64 u1 = u0 + step;
     u64 os, ns;
     u32 on, nn;
     // the first round's pair and offsets are in flight while the tables are copied to LDS
-    load_off(load_pair(u0 + lane), owner && u0 + lane < n_upd, os, ns, on, nn);
-    for (u32 i = 16 * lane; i < to.bytes; i += 16 * FD_NT) *(u32x4*)(s_tab + i) = *(gp128)(tab_base + i);
-    mp_tab_to_lds();
+    fd_load_off(ooff, noff, fd_load_pair(pairs, u0 + lane, lim, owner), owner && u0 + lane < n_upd, os, ns, on, nn);
+    fd_tab_copy(s_tab, to, tab_base);
     if (owner) s_res[lane] = 0;
     if (lane == 0) s_ntask = 0;
-    FdTabT<3> tb;
-    tb.n_keys = tg.n_keys; tb.words = tg.words; tb.n_lo = tg.n_lo; tb.n_ln = tg.n_ln; tb.maxv = tg.maxv;
-    typedef __attribute__((address_space(3))) u8* l8;
-    const l8 lt = (l8)s_tab;
-    tb.leg_o = (typename ASP<3, u32>::type)(lt + to.leg_o);
-    tb.leg_n = (typename ASP<3, u32>::type)(lt + to.leg_n);
-    tb.map_o = (typename ASP<3, i16>::type)(lt + to.map_o);
-    tb.map_n = (typename ASP<3, i16>::type)(lt + to.map_n);
-    tb.cmp = (typename ASP<3, u64>::type)(lt + to.cmp);
-    tb.aligned = (typename ASP<3, u16>::type)(lt + to.aligned);
-    tb.key_of_val = (typename ASP<3, i16>::type)(lt + to.key_of_val);
+    const FdTabT<3> tb = fd_tab_at<3>((ASP<3, u8>::type)s_tab, tg, to);
     const FdQueue queue{(lds_u64p)s_task, (lds_u32p)&s_ntask, TCAP};
     const u32 img0 = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_img;
     // window descriptors of one round, in the owner lanes' registers: head chunk and last chunk of
@@ -1266,7 +1294,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, 
     // and round r's queued payloads are loaded together.
     put_desc(os, on, ns, nn, owner && u0 + lane < n_upd);
     stage();
-    uint2 pr_n = load_pair(u1 + lane);
+    uint2 pr_n = fd_load_pair(pairs, u1 + lane, lim, owner);
     __syncthreads();  // vmcnt(0) + barrier: round 0's windows have landed
     for (;;) {
         const u64 u = u0 + lane;
@@ -1275,7 +1303,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, 
         u64 os_n = 0, ns_n = 0, u2 = end;
         u32 on_n = 0, nn_n = 0;
         if (more) {
-            load_off(pr_n, owner && u1 + lane < n_upd, os_n, ns_n, on_n, nn_n);
+            fd_load_off(ooff, noff, pr_n, owner && u1 + lane < n_upd, os_n, ns_n, on_n, nn_n);
             u2 = u1 + step;
         }
         // ---- parse ----
@@ -1302,7 +1330,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, 
         if (more) {
             put_desc(os_n, on_n, ns_n, nn_n, owner && u1 + lane < n_upd);
             stage();
-            pr_n = load_pair(u2 + lane);
+            pr_n = fd_load_pair(pairs, u2 + lane, lim, owner);
         }
         // ---- the queued payloads, 16 lanes per payload ----
 #if KD_FD_PROBE_NOCMP  // timing probe only (results invalid): queued payloads dropped
@@ -1311,6 +1339,8 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff(const u8* __restrict__ od, 
         const u32 nt = min(s_ntask, TCAP);
 #endif
         // (M payloads per 16-lane group per pass: their loads share one memory round trip)
+        // This loop and the round's end below are written out in k_fdwalk too: through a shared helper
+        // this kernel's stream changes (profiles/fielddiff_shared/asm_compare.txt).  Change both.
         constexpr int M = TM, G = TG, NG = 64 / TG;
         for (u32 t = (u32)lane / G; t < nt; t += NG * M) {
             u64 ta[M], tbb[M], tx[M];
@@ -1399,6 +1429,22 @@ __device__ __forceinline__ void fd_load_tile(FdTile& f, u64 tile, u64 n_upd, con
     f.ncn = (u32)min<u64>((((u64)nd + sn1) - f.cn + 15) >> 4, CAPC);
 }
 
+// PF: chunk 64 p + lane of a tile's two spans (the old span's chunks, then the new span's) passes
+// through this lane's buf[p]: LOAD reads it from global memory, else it is written into the image
+template <bool LOAD, int N>
+__device__ __forceinline__ void fd_span_chunks(const FdTile& f, u32x4 (&buf)[N], u32 img_o, u32 img_n) {
+    typedef __attribute__((address_space(3))) u32x4* l128;
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int p = 0; p < N; p++) {
+        const u32 i = 64 * p + lane;
+        const bool o = i < f.nco, n = !o && i < f.nco + f.ncn;
+        if (!(o || n)) continue;
+        if (LOAD) buf[p] = *(gp128)(o ? f.co + 16ull * i : f.cn + 16ull * (i - f.nco));
+        else *(l128)(size_t)(o ? img_o + 16 * i : img_n + 16 * (i - f.nco)) = buf[p];
+    }
+}
+
 // PF: the spans of the next tile are loaded into registers (PL chunks per lane: the old span's
 // chunks, then the new span's) while the current tile is parsed from LDS, and written to LDS after
 // it — plain loads, so no wait on them precedes the parse's LDS reads (an LDS-DMA in flight makes
@@ -1417,44 +1463,21 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_s(const u8* __restrict__ od
     __shared__ u32 s_dummy;
     extern __shared__ __attribute__((aligned(16))) u8 s_tab[];
     const int lane = threadIdx.x;
-    const u64 n_upd = n_upd_dev ? min(fd_dev_count(n_upd_dev, n_part), n_upd_host ? n_upd_host : ~0ull) : n_upd_host;
+    const u64 n_upd = fd_count(n_upd_host, n_upd_dev, n_part).end;  // (no pairs: the capacity only clamps the device count)
     const u64 ntiles = (n_upd + T - 1) / T;
     if ((u64)blockIdx.x >= ntiles) return;  // wave-uniform
-    for (u32 i = 16 * lane; i < to.bytes; i += 16 * FD_NT) *(u32x4*)(s_tab + i) = *(gp128)(tab_base + i);
-    mp_tab_to_lds();
-    FdTabT<3> tb;
-    tb.n_keys = tg.n_keys; tb.words = tg.words; tb.n_lo = tg.n_lo; tb.n_ln = tg.n_ln; tb.maxv = tg.maxv;
-    typedef __attribute__((address_space(3))) u8* l8;
-    const l8 lt = (l8)s_tab;
-    tb.leg_o = (typename ASP<3, u32>::type)(lt + to.leg_o);
-    tb.leg_n = (typename ASP<3, u32>::type)(lt + to.leg_n);
-    tb.map_o = (typename ASP<3, i16>::type)(lt + to.map_o);
-    tb.map_n = (typename ASP<3, i16>::type)(lt + to.map_n);
-    tb.cmp = (typename ASP<3, u64>::type)(lt + to.cmp);
-    tb.aligned = (typename ASP<3, u16>::type)(lt + to.aligned);
-    tb.key_of_val = (typename ASP<3, i16>::type)(lt + to.key_of_val);
+    fd_tab_copy(s_tab, to, tab_base);
+    const FdTabT<3> tb = fd_tab_at<3>((ASP<3, u8>::type)s_tab, tg, to);
     const FdQueue none{(lds_u64p) nullptr, (lds_u32p)&s_dummy, 0};  // payloads compare in place
     const u32 img_o = (u32)(size_t)(const __attribute__((address_space(3))) u32x4*)s_img;
     const u32 img_n = img_o + 16 * CAPC;
-    typedef __attribute__((address_space(3))) u32x4* l128;
     u64 tile = blockIdx.x;
     FdTile cur, nxt;
     fd_load_tile<T, CAPC>(cur, tile, n_upd, od, ooff, nd, noff);
     u32x4 buf[PF ? PL : 1];
     if (PF) {  // the first tile's spans through registers too
-#pragma unroll
-        for (int p = 0; p < PL; p++) {
-            const u32 i = 64 * p + lane;
-            const bool o = i < cur.nco, n = !o && i < cur.nco + cur.ncn;
-            const u64 src = o ? cur.co + 16ull * i : cur.cn + 16ull * (i - cur.nco);
-            if (o || n) buf[p] = *(gp128)src;
-        }
-#pragma unroll
-        for (int p = 0; p < PL; p++) {
-            const u32 i = 64 * p + lane;
-            const bool o = i < cur.nco, n = !o && i < cur.nco + cur.ncn;
-            if (o || n) *(l128)(size_t)(o ? img_o + 16 * i : img_n + 16 * (i - cur.nco)) = buf[p];
-        }
+        fd_span_chunks<true>(cur, buf, img_o, img_n);
+        fd_span_chunks<false>(cur, buf, img_o, img_n);
     }
     u64 nt = tile + gridDim.x;
     if (PF && nt < ntiles) fd_load_tile<T, CAPC>(nxt, nt, n_upd, od, ooff, nd, noff);
@@ -1462,15 +1485,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_s(const u8* __restrict__ od
         const bool more = PF && nt < ntiles;  // wave-uniform
         if (PF) {
             // the next tile's spans into registers (its offsets were loaded during the last tile)
-            if (more) {
-#pragma unroll
-                for (int p = 0; p < PL; p++) {
-                    const u32 i = 64 * p + lane;
-                    const bool o = i < nxt.nco, n = !o && i < nxt.nco + nxt.ncn;
-                    const u64 src = o ? nxt.co + 16ull * i : nxt.cn + 16ull * (i - nxt.nco);
-                    if (o || n) buf[p] = *(gp128)src;
-                }
-            }
+            if (more) fd_span_chunks<true>(nxt, buf, img_o, img_n);
         } else {
             for (u32 k = 0; k < cur.nco; k += FD_NT)
                 if (k + lane < cur.nco)
@@ -1522,12 +1537,7 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_s(const u8* __restrict__ od
         const u64 nn = nt + gridDim.x;
         FdTile aft;
         if (nn < ntiles) fd_load_tile<T, CAPC>(aft, nn, n_upd, od, ooff, nd, noff);
-#pragma unroll
-        for (int p = 0; p < PL; p++) {
-            const u32 i = 64 * p + lane;
-            const bool o = i < nxt.nco, n = !o && i < nxt.nco + nxt.ncn;
-            if (o || n) *(l128)(size_t)(o ? img_o + 16 * i : img_n + 16 * (i - nxt.nco)) = buf[p];
-        }
+        fd_span_chunks<false>(nxt, buf, img_o, img_n);
         cur = nxt;
         nt = nn;
         if (nn < ntiles) nxt = aft;
@@ -1562,56 +1572,28 @@ __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WP
                                                   FdTab tg, FdTabOff to, const u8* __restrict__ tab_base,
                                                   u64* __restrict__ masks, u8* __restrict__ status) {
     constexpr u32 TCAP = FD_NT;  // queued payload compares per round (then a lane compares alone)
+    static_assert(FD_NT <= 64, "packed fields: task words hold the owner lane in 6 bits");
     __shared__ u64 s_task[2 * TCAP];
     __shared__ u64 s_res[FD_NT];  // mask bits (keys < 64) found by the cooperative compares
     __shared__ u32 s_ntask;
     extern __shared__ __attribute__((aligned(16))) u8 s_tab[];
     const int lane = threadIdx.x;
-    const bool spec = n_upd_dev && n_upd_host;
-    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
-    const u64 lim = spec ? n_upd_host : n_upd;
-    const u64 end = min(lim, n_upd);
+    const u64 end = fd_count(n_upd_host, n_upd_dev, n_part).end;
     const u64 step = (u64)gridDim.x * FD_NT;
     u64 u0 = (u64)blockIdx.x * FD_NT;
     if (u0 >= end) return;  // wave-uniform
     // the arenas' ends: no load crosses them
     const u64 olim = (u64)od + ooff[n_ent_o], nlim = (u64)nd + noff[n_ent_n];
-    auto load_pair = [&](u64 uu) {
-        uint2 p = make_uint2((u32)uu, (u32)uu);
-        if (pairs && uu < end) p = pairs[uu];
-        return p;
-    };
-    auto load_off = [&](uint2 p, bool a, u64& os_, u64& ns_, u32& on_, u32& nn_) {
-        os_ = ns_ = 0;
-        on_ = nn_ = 0;
-        if (a) {
-            os_ = ooff[p.x];
-            ns_ = noff[p.y];
-            on_ = (u32)(ooff[p.x + 1] - os_);
-            nn_ = (u32)(noff[p.y + 1] - ns_);
-        }
-    };
     u64 u1 = u0 + step;
     u64 os, ns;
     u32 on, nn;
-    load_off(load_pair(u0 + lane), u0 + lane < end, os, ns, on, nn);
-    for (u32 i = 16 * lane; i < to.bytes; i += 16 * FD_NT) *(u32x4*)(s_tab + i) = *(gp128)(tab_base + i);
-    mp_tab_to_lds();
+    fd_load_off(ooff, noff, fd_load_pair(pairs, u0 + lane, end, true), u0 + lane < end, os, ns, on, nn);
+    fd_tab_copy(s_tab, to, tab_base);
     s_res[lane] = 0;
     if (lane == 0) s_ntask = 0;
-    FdTabT<3> tb;
-    tb.n_keys = tg.n_keys; tb.words = tg.words; tb.n_lo = tg.n_lo; tb.n_ln = tg.n_ln; tb.maxv = tg.maxv;
-    typedef __attribute__((address_space(3))) u8* l8;
-    const l8 lt = (l8)s_tab;
-    tb.leg_o = (typename ASP<3, u32>::type)(lt + to.leg_o);
-    tb.leg_n = (typename ASP<3, u32>::type)(lt + to.leg_n);
-    tb.map_o = (typename ASP<3, i16>::type)(lt + to.map_o);
-    tb.map_n = (typename ASP<3, i16>::type)(lt + to.map_n);
-    tb.cmp = (typename ASP<3, u64>::type)(lt + to.cmp);
-    tb.aligned = (typename ASP<3, u16>::type)(lt + to.aligned);
-    tb.key_of_val = (typename ASP<3, i16>::type)(lt + to.key_of_val);
+    const FdTabT<3> tb = fd_tab_at<3>((ASP<3, u8>::type)s_tab, tg, to);
     const FdQueue queue{(lds_u64p)s_task, (lds_u32p)&s_ntask, TCAP};
-    uint2 pr_n = load_pair(u1 + lane);
+    uint2 pr_n = fd_load_pair(pairs, u1 + lane, end, true);
     __syncthreads();  // the tables are in LDS
     for (;;) {
         const u64 u = u0 + lane;
@@ -1620,7 +1602,7 @@ __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WP
         u64 os_n = 0, ns_n = 0, u2 = end;
         u32 on_n = 0, nn_n = 0;
         if (more) {  // the next round's offsets are in flight during this round's walk
-            load_off(pr_n, u1 + lane < end, os_n, ns_n, on_n, nn_n);
+            fd_load_off(ooff, noff, pr_n, u1 + lane < end, os_n, ns_n, on_n, nn_n);
             u2 = u1 + step;
         }
         u64 mk[4] = {0, 0, 0, 0};
@@ -1634,7 +1616,7 @@ __global__ __launch_bounds__(FD_NT) __attribute__((amdgpu_waves_per_eu(KD_FDW_WP
             st = diff_one_f<1>(A, B, tb, mk, m, queue);
         }
         __syncthreads();  // the walk is done: the queue is complete
-        if (more) pr_n = load_pair(u2 + lane);
+        if (more) pr_n = fd_load_pair(pairs, u2 + lane, end, true);
         // ---- the queued payloads, TG lanes per payload, TM per group per pass ----
         const u32 nt = min(s_ntask, TCAP);
         constexpr int M = TM, G = TG, NG = 64 / TG;
@@ -1685,17 +1667,15 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_g(const u8* __restrict__ od
                                                        const u64* __restrict__ n_upd_dev, int n_part, FdTab tb,
                                                        u64* __restrict__ masks, u8* __restrict__ status) {
     const int lane = threadIdx.x;
-    const bool spec = n_upd_dev && n_upd_host;
-    const u64 n_upd = n_upd_dev ? fd_dev_count(n_upd_dev, n_part) : n_upd_host;
-    const u64 lim = spec ? n_upd_host : n_upd;
+    const FdCount cnt = fd_count(n_upd_host, n_upd_dev, n_part);
+    const u64 n_upd = cnt.n_upd, lim = cnt.lim;
     for (u64 u0 = (u64)blockIdx.x * FD_NT; u0 < lim; u0 += (u64)gridDim.x * FD_NT) {
         const u64 u = u0 + lane;
-        uint2 pr = make_uint2((u32)u, (u32)u);
-        if (pairs && u < lim) pr = pairs[u];
+        const uint2 pr = fd_load_pair(pairs, u, lim, true);
         if (u0 >= n_upd || u >= n_upd) break;
-        const u64 os = ooff[pr.x], ns = noff[pr.y];
-        const u32 on = (u32)(ooff[pr.x + 1] - os);
-        const u32 nn = (u32)(noff[pr.y + 1] - ns);
+        u64 os, ns;
+        u32 on, nn;
+        fd_load_off(ooff, noff, pr, true, os, ns, on, nn);
         u64* m = masks + u * tb.words;
         for (int w = 4; w < tb.words; w++) m[w] = 0;
         u64 mk[4] = {0, 0, 0, 0};
@@ -1706,9 +1686,149 @@ __global__ __launch_bounds__(FD_NT) void k_fielddiff_g(const u8* __restrict__ od
     }
 }
 
+// ---- host: the packed tables, staging, the launch variant (chosen once) and the launch ----
+// The device tables of one call from its legend maps, packed for one upload (a pure host function):
+// the bytes, the offsets of the tables the kernels read, and maxv, the row length of key_of_val.
+struct FdHostTab { std::vector<u8> bytes; FdTabOff off; int maxv; };
+static FdHostTab fd_pack_tables(const kd_legend_maps* mp) {
+    const int nk = mp->n_keys, nlo = mp->n_leg_old, nln = mp->n_leg_new;
+    auto compared = [&](int k) { return (mp->cmp_mask[k >> 6] >> (k & 63)) & 1; };
+    // per old legend: its value count = max value index + 1 over its map (non-pk columns), and
+    // need = 1 + the largest value index of a compared key
+    FdHostTab t{{}, {}, 1};
+    std::vector<u32> nvo(nlo, 0), need(nlo, 0);
+    for (int l = 0; l < nlo; l++) {
+        for (int k = 0; k < nk; k++) {
+            const int s = mp->map_old[(size_t)l * nk + k];
+            if (s >= 0 && (u32)s + 1 > nvo[l]) nvo[l] = (u32)s + 1;
+            if (s >= 0 && compared(k) && (u32)s + 1 > need[l]) need[l] = (u32)s + 1;
+        }
+        t.maxv = std::max<int>(t.maxv, (int)nvo[l]);
+    }
+    std::vector<u16> aligned((size_t)nlo * nln, 0);  // 0, or 1 + need[old legend]
+    for (int a = 0; a < nlo; a++)
+        for (int b = 0; b < nln; b++) {
+            bool ok = true;
+            for (int k = 0; k < nk && ok; k++) {
+                if (!compared(k)) continue;
+                const int so = mp->map_old[(size_t)a * nk + k], sn = mp->map_new[(size_t)b * nk + k];
+                // identical map entries (value index, None or pk on both sides); a _NULL key
+                // (absent from a schema) always compares changed, so it forces the general path
+                ok = so == sn && so != -1;
+            }
+            aligned[(size_t)a * nln + b] = ok ? (u16)(1 + need[a]) : 0;
+        }
+    std::vector<i16> kov((size_t)nlo * t.maxv, -1);
+    for (int l = 0; l < nlo; l++)
+        for (int k = 0; k < nk; k++) {
+            const int s = mp->map_old[(size_t)l * nk + k];
+            if (compared(k) && s >= 0 && s < t.maxv) kov[(size_t)l * t.maxv + s] = (i16)k;
+        }
+    // the layout: each table at the next 16-B boundary, the value counts last
+    const void* src[8] = {mp->leg_old_hex, mp->leg_new_hex, mp->map_old, mp->map_new, mp->cmp_mask, aligned.data(), kov.data(), nvo.data()};
+    const size_t len[8] = {(size_t)nlo * 40, (size_t)nln * 40, (size_t)nlo * nk * 2, (size_t)nln * nk * 2, (size_t)mp->words * 8,
+                           aligned.size() * 2, kov.size() * 2, (size_t)nlo * 4};
+    size_t at[9] = {0};
+    for (int i = 0; i < 8; i++) at[i + 1] = (at[i] + len[i] + 15) & ~(size_t)15;
+    t.bytes.assign(at[8], 0);
+    for (int i = 0; i < 8; i++)
+        if (len[i]) std::memcpy(&t.bytes[at[i]], src[i], len[i]);
+    t.off = {(u32)at[0], (u32)at[1], (u32)at[2], (u32)at[3], (u32)at[4], (u32)at[5], (u32)at[6], (u32)at[8]};
+    return t;
+}
+
+// the kernel arguments of one launch (each kernel takes the ones it declares)
+struct FdArgs {
+    const u8 *od, *nd, *tab;
+    const u64 *ooff, *noff, *d_n_upd;
+    const uint2* pu;
+    u64 n_upd, n_ent_o, n_ent_n;
+    int n_part;
+    FdTab tb;
+    FdTabOff to;
+    u64* masks;
+    u8* status;
+};
+
+// One launch variant: the occupancy query, the grid and the launch all read it.
+struct FdVariant {
+    const void* fn;  // the kernel, for the occupancy calculator
+    u64 upr;         // updates per round (per tile)
+    int cap;         // resident workgroups per CU at most (the measured optimum)
+    size_t lds;      // dynamic LDS: the packed tables
+    void (*go)(unsigned blocks, size_t lds, hipStream_t s, const FdArgs& a);
+};
+template <auto K>  // k_fielddiff<shape, MR>
+static void fd_go_w(unsigned blocks, size_t lds, hipStream_t s, const FdArgs& a) {
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(FD_NT), lds, s, a.od, a.ooff, a.nd, a.noff, a.pu, a.n_upd, a.d_n_upd, a.n_part, a.tb,
+                       a.to, a.tab, a.masks, a.status);
+}
+template <auto K>  // k_fielddiff_s: no pairs
+static void fd_go_s(unsigned blocks, size_t lds, hipStream_t s, const FdArgs& a) {
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(FD_NT), lds, s, a.od, a.ooff, a.nd, a.noff, a.n_upd, a.d_n_upd, a.n_part, a.tb, a.to,
+                       a.tab, a.masks, a.status);
+}
+template <auto K>  // k_fdwalk: the arenas' entry counts too
+static void fd_go_walk(unsigned blocks, size_t lds, hipStream_t s, const FdArgs& a) {
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(FD_NT), lds, s, a.od, a.ooff, a.nd, a.noff, a.pu, a.n_upd, a.d_n_upd, a.n_part,
+                       a.n_ent_o, a.n_ent_n, a.tb, a.to, a.tab, a.masks, a.status);
+}
+static void fd_go_g(unsigned blocks, size_t lds, hipStream_t s, const FdArgs& a) {  // the tables stay in global memory
+    hipLaunchKernelGGL(k_fielddiff_g, dim3(blocks), dim3(FD_NT), lds, s, a.od, a.ooff, a.nd, a.noff, a.pu,
+                       a.n_upd, a.d_n_upd, a.n_part, a.tb, a.masks, a.status);
+}
+template <int UPR, int NH, int NTL, int TM, int TG, int TS>
+static FdVariant fd_windowed(int W, size_t lds) {  // (mask words in registers: one for up to 64 union keys, else four)
+    constexpr auto K1 = k_fielddiff<UPR, NH, NTL, TM, TG, TS, 1>, K4 = k_fielddiff<UPR, NH, NTL, TM, TG, TS, 4>;
+    if (W == 1) return {(const void*)K1, UPR, KD_FD_CAP, lds, fd_go_w<K1>};
+    return {(const void*)K4, UPR, KD_FD_CAP, lds, fd_go_w<K4>};
+}
+template <int T, int CAPB>
+static FdVariant fd_streamed(size_t lds) {
+    constexpr auto K = k_fielddiff_s<T, CAPB, KD_FD_SPF>;
+    return {(const void*)K, T, 16, lds, fd_go_s<K>};
+}
+static FdVariant fd_choose(bool walk, bool stream, bool lds_tab, bool small, int W, size_t tab_bytes) {
+    constexpr auto KW = k_fdwalk<KD_FDW_SHAPE>;
+    if (walk) return {(const void*)KW, FD_NT, KD_FDW_CAP, tab_bytes, fd_go_walk<KW>};
+    if (stream) return fd_streamed<KD_FD_SSHAPE>(tab_bytes);
+    if (!lds_tab) return {(const void*)k_fielddiff_g, FD_NT, KD_FD_CAP, 0, fd_go_g};
+    return small ? fd_windowed<KD_FD_SHAPE_S>(W, tab_bytes) : fd_windowed<KD_FD_SHAPE_L>(W, tab_bytes);
+}
+
+static int fd_launch(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const FdArgs& a) {
+    const u64 work = a.d_n_upd ? (a.n_upd ? a.n_upd : (u64)1 << 22) : a.n_upd;
+    // typical blob size: kd_blobs.size_hint, or the mean of host arenas
+    auto typical = [](const kd_blobs* b) -> u64 {
+        if (b->size_hint) return b->size_hint;
+        if (b->mem == KD_MEM_HOST && b->n) return (b->off[b->n] - b->off[0] + b->n - 1) / b->n;
+        return 256;
+    };
+    const bool lds_tab = a.to.bytes <= FD_TAB_LDS_MAX;
+    // window shape from the typical blob: small features (points, ~90-150 B) fit a long head window
+    // whole; larger ones (polygons) get head + tail windows around their geometry
+    const bool small = std::max(typical(ob), typical(nb)) <= 144;
+    // the streamed kernel: contiguous update arenas (no pairs) of larger blobs; the fd_stream option
+    // 0 / 1 forces it off / on
+    const int stream_env = ctx->opt.fd_stream;
+    const bool stream = lds_tab && a.pu == nullptr && (stream_env >= 0 ? stream_env > 0 : !small && KD_FD_STREAM_DEFAULT);
+    // the walked kernel (no LDS images; slower: DESIGN §3.2): the fd_walk option 1 forces it
+    const bool walk = lds_tab && !stream && ctx->opt.fd_walk > 0;
+    const FdVariant v = fd_choose(walk, stream, lds_tab, small, a.tb.words, a.to.bytes);
+    // The kernel loops over rounds (grid stride), so its grid is the resident set (occupancy
+    // calculator for this launch's LDS), capped at the measured optimum.
+    // (the calculator can count one block per CU more than becomes resident: DESIGN.md §3.2)
+    int per_cu = 0;
+    KD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v.fn, FD_NT, v.lds));
+    per_cu = std::max(1, std::min(per_cu, v.cap));
+    const unsigned blocks = (unsigned)std::max<u64>(1, std::min<u64>((work + v.upr - 1) / v.upr, (u64)ctx->n_cu * (u64)per_cu));
+    return launch(ctx, "k_fielddiff", [&] { v.go(blocks, v.lds, ctx->stream, a); });
+}
+
 int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const uint32_t* pu, uint64_t n_upd,
                      const uint64_t* d_n_upd, int n_part, uint32_t pairs_mem, const kd_legend_maps* mp, uint64_t* masks,
                      uint8_t* status, uint32_t out_mem) {
+    // ---- argument checks ----
     KD_CHECK(ctx && ob && nb && mp && masks && status, "kd_fielddiff: NULL argument");
     KD_CHECK(mp->n_keys >= 0 && mp->words == (mp->n_keys + 63) / 64 && mp->words >= 1, "kd_fielddiff: bad words");
     KD_CHECK(mp->n_leg_old > 0 && mp->n_leg_new > 0 && mp->n_leg_old <= 4096 && mp->n_leg_new <= 4096,
@@ -1717,162 +1837,40 @@ int fielddiff_device(kd_ctx* ctx, const kd_blobs* ob, const kd_blobs* nb, const 
     KD_CHECK(n_part >= 0 && n_part <= 64 && (n_part == 0 || d_n_upd), "kd_fielddiff: bad partial counters");
     KD_HIP(hipSetDevice(ctx->device));
     int rc;
-    // ---- host tables -> device ----
-    const int nk = mp->n_keys, nlo = mp->n_leg_old, nln = mp->n_leg_new, W = mp->words;
-    // value count per old legend = max value index + 1 over its map (non-pk columns)
-    int maxv = 1;
-    std::vector<u32> nvo(nlo, 0);
-    for (int l = 0; l < nlo; l++)
-        for (int k = 0; k < nk; k++) {
-            int s = mp->map_old[(size_t)l * nk + k];
-            if (s >= 0 && (u32)s + 1 > nvo[l]) nvo[l] = (u32)s + 1;
-        }
-    for (int l = 0; l < nlo; l++) maxv = std::max<int>(maxv, (int)nvo[l]);
-    std::vector<u32> need(nlo, 0);  // per old legend: 1 + the largest value index of a compared key
-    for (int l = 0; l < nlo; l++)
-        for (int k = 0; k < nk; k++) {
-            if (!((mp->cmp_mask[k >> 6] >> (k & 63)) & 1)) continue;
-            int s = mp->map_old[(size_t)l * nk + k];
-            if (s >= 0 && (u32)s + 1 > need[l]) need[l] = (u32)s + 1;
-        }
-    std::vector<u16> aligned((size_t)nlo * nln, 0);  // 0, or 1 + need[old legend]
-    for (int a = 0; a < nlo; a++)
-        for (int b = 0; b < nln; b++) {
-            bool ok = true;
-            for (int k = 0; k < nk && ok; k++) {
-                if (!((mp->cmp_mask[k >> 6] >> (k & 63)) & 1)) continue;
-                int so = mp->map_old[(size_t)a * nk + k], sn = mp->map_new[(size_t)b * nk + k];
-                // identical map entries (value index, None or pk on both sides); a _NULL key
-                // (absent from a schema) always compares changed, so it forces the general path
-                ok = so == sn && so != -1;
-            }
-            aligned[(size_t)a * nln + b] = ok ? (u16)(1 + need[a]) : 0;
-        }
-    std::vector<i16> kov((size_t)nlo * maxv, -1);
-    for (int l = 0; l < nlo; l++)
-        for (int k = 0; k < nk; k++) {
-            if (!((mp->cmp_mask[k >> 6] >> (k & 63)) & 1)) continue;
-            int s = mp->map_old[(size_t)l * nk + k];
-            if (s >= 0 && s < maxv) kov[(size_t)l * maxv + s] = (i16)k;
-        }
-    // one packed upload
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t o_lo = 0, o_ln = al(o_lo + (size_t)nlo * 40), o_mo = al(o_ln + (size_t)nln * 40),
-           o_mn = al(o_mo + (size_t)nlo * nk * 2), o_cmp = al(o_mn + (size_t)nln * nk * 2),
-           o_al = al(o_cmp + (size_t)W * 8), o_kov = al(o_al + aligned.size() * 2), o_nv = al(o_kov + kov.size() * 2),
-           o_end = al(o_nv + (size_t)nlo * 4);
-    std::vector<u8> h(o_end, 0);
-    std::memcpy(&h[o_lo], mp->leg_old_hex, (size_t)nlo * 40);
-    std::memcpy(&h[o_ln], mp->leg_new_hex, (size_t)nln * 40);
-    std::memcpy(&h[o_mo], mp->map_old, (size_t)nlo * nk * 2);
-    std::memcpy(&h[o_mn], mp->map_new, (size_t)nln * nk * 2);
-    std::memcpy(&h[o_cmp], mp->cmp_mask, (size_t)W * 8);
-    std::memcpy(&h[o_al], aligned.data(), aligned.size() * 2);
-    if (!kov.empty()) std::memcpy(&h[o_kov], kov.data(), kov.size() * 2);
-    std::memcpy(&h[o_nv], nvo.data(), (size_t)nlo * 4);
+    FdArgs a;
+    a.n_upd = n_upd; a.d_n_upd = d_n_upd; a.n_part = n_part; a.masks = masks; a.status = status;
+    // ---- the packed tables to the device (uploaded when they changed) ----
+    FdHostTab h = fd_pack_tables(mp);
     void* dt;
-    if ((rc = ensure(ctx, "fd.tab", o_end, &dt))) return rc;
-    if (ctx->fd_tab != h) {
-        ctx->fd_tab.swap(h);  // keep the source alive until the stream has consumed it
-        KD_HIP(hipMemcpyAsync(dt, ctx->fd_tab.data(), o_end, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ensure(ctx, "fd.tab", h.bytes.size(), &dt))) return rc;
+    if (ctx->fd_tab != h.bytes) {
+        ctx->fd_tab.swap(h.bytes);  // keep the source alive until the stream has consumed it
+        KD_HIP(hipMemcpyAsync(dt, ctx->fd_tab.data(), ctx->fd_tab.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    FdTab tb;
-    tb.n_keys = nk; tb.words = W; tb.n_lo = nlo; tb.n_ln = nln; tb.maxv = maxv;
-    const u8* base = (const u8*)dt;
-    tb.leg_o = (const u32*)(base + o_lo); tb.leg_n = (const u32*)(base + o_ln);
-    tb.map_o = (const i16*)(base + o_mo); tb.map_n = (const i16*)(base + o_mn);
-    tb.cmp = (const u64*)(base + o_cmp); tb.aligned = (const u16*)(base + o_al);
-    tb.key_of_val = (const i16*)(base + o_kov);
-
-    // ---- inputs ----
-    const void *d_od, *d_ooff, *d_nd, *d_noff, *d_pu = nullptr;
-    u64 ob_bytes = 0, nb_bytes = 0;
-    if (ob->mem == KD_MEM_HOST) ob_bytes = ob->off[ob->n];
-    if (nb->mem == KD_MEM_HOST) nb_bytes = nb->off[nb->n];
-    if ((rc = stage_in(ctx, "fd.ooff", ob->off, (ob->n + 1) * 8, ob->mem, &d_ooff))) return rc;
-    if ((rc = stage_in(ctx, "fd.od", ob->data, ob_bytes ? ob_bytes : 1, ob->mem, &d_od))) return rc;
-    if ((rc = stage_in(ctx, "fd.noff", nb->off, (nb->n + 1) * 8, nb->mem, &d_noff))) return rc;
-    if ((rc = stage_in(ctx, "fd.nd", nb->data, nb_bytes ? nb_bytes : 1, nb->mem, &d_nd))) return rc;
+    a.tab = (const u8*)dt; a.to = h.off;
+    a.tb.n_keys = mp->n_keys; a.tb.words = mp->words; a.tb.n_lo = mp->n_leg_old; a.tb.n_ln = mp->n_leg_new; a.tb.maxv = h.maxv;
+    a.tb = fd_tab_at<-1>(a.tab, a.tb, a.to);
+    // ---- inputs, and device outputs for a host caller ----
+    const u64 ob_bytes = ob->mem == KD_MEM_HOST ? ob->off[ob->n] : 0, nb_bytes = nb->mem == KD_MEM_HOST ? nb->off[nb->n] : 0;
+    if ((rc = stage_in(ctx, "fd.ooff", ob->off, (ob->n + 1) * 8, ob->mem, (const void**)&a.ooff))) return rc;
+    if ((rc = stage_in(ctx, "fd.od", ob->data, ob_bytes ? ob_bytes : 1, ob->mem, (const void**)&a.od))) return rc;
+    if ((rc = stage_in(ctx, "fd.noff", nb->off, (nb->n + 1) * 8, nb->mem, (const void**)&a.noff))) return rc;
+    if ((rc = stage_in(ctx, "fd.nd", nb->data, nb_bytes ? nb_bytes : 1, nb->mem, (const void**)&a.nd))) return rc;
+    a.n_ent_o = ob->n; a.n_ent_n = nb->n; a.pu = nullptr;
     if (d_n_upd) {
         KD_CHECK(pu == nullptr || pairs_mem == KD_MEM_DEVICE, "kd_fielddiff: device count needs device pairs");
-        d_pu = pu;  // device pairs with a device count; n_upd is then the capacity (0 = unknown)
+        a.pu = (const uint2*)pu;  // device pairs with a device count; n_upd is then the capacity (0 = unknown)
     } else if (pu && n_upd) {
-        if ((rc = stage_in(ctx, "fd.pu", pu, n_upd * 8, pairs_mem, &d_pu))) return rc;
+        if ((rc = stage_in(ctx, "fd.pu", pu, n_upd * 8, pairs_mem, (const void**)&a.pu))) return rc;
     }
-    u64 *d_masks = masks;
-    u8* d_status = status;
     if (out_mem == KD_MEM_HOST && n_upd && !d_n_upd) {
-        void *a, *b;
-        if ((rc = ensure(ctx, "fd.masks", n_upd * W * 8, &a))) return rc;
-        if ((rc = ensure(ctx, "fd.status", n_upd, &b))) return rc;
-        d_masks = (u64*)a;
-        d_status = (u8*)b;
+        if ((rc = ensure(ctx, "fd.masks", n_upd * mp->words * 8, (void**)&a.masks))) return rc;
+        if ((rc = ensure(ctx, "fd.status", n_upd, (void**)&a.status))) return rc;
     }
     if (n_upd == 0 && d_n_upd == nullptr) return KD_OK;
-    u64 work = d_n_upd ? (n_upd ? n_upd : (u64)1 << 22) : n_upd;
-    // typical blob size: kd_blobs.size_hint, or the mean of host arenas
-    auto typical = [](const kd_blobs* b) -> u64 {
-        if (b->size_hint) return b->size_hint;
-        if (b->mem == KD_MEM_HOST && b->n) return (b->off[b->n] - b->off[0] + b->n - 1) / b->n;
-        return 256;
-    };
-    const u64 typ = std::max(typical(ob), typical(nb));
-    FdTabOff to;
-    to.leg_o = (u32)o_lo; to.leg_n = (u32)o_ln; to.map_o = (u32)o_mo; to.map_n = (u32)o_mn; to.cmp = (u32)o_cmp;
-    to.aligned = (u32)o_al; to.key_of_val = (u32)o_kov; to.bytes = (u32)o_end;
-    const bool lds_tab = o_end <= FD_TAB_LDS_MAX;
-    // window shape from the typical blob: small features (points, ~90-150 B) fit a long head window
-    // whole; larger ones (polygons) get head + tail windows around their geometry
-    const bool small = typ <= 144;
-    // the streamed kernel: contiguous update arenas (no pairs) of larger blobs; the fd_stream option
-    // 0 / 1 forces it off / on
-    const int stream_env = ctx->opt.fd_stream;
-    const bool stream = lds_tab && d_pu == nullptr && (stream_env >= 0 ? stream_env > 0 : !small && KD_FD_STREAM_DEFAULT);
-    // the walked kernel (no LDS images; slower: DESIGN §3.2): the fd_walk option 1 forces it
-    const int walk_env = ctx->opt.fd_walk;
-    const bool walk = lds_tab && !stream && walk_env > 0;
-    // The kernel loops over rounds (grid stride), so its grid is the resident set (occupancy
-    // calculator for this launch's LDS), capped at the measured optimum.
-    const void* kern = walk ? (const void*)k_fdwalk<KD_FDW_SHAPE>
-                       : stream ? (const void*)k_fielddiff_s<KD_FD_SSHAPE, KD_FD_SPF>
-                       : !lds_tab ? (const void*)k_fielddiff_g
-                       : small ? (W == 1 ? (const void*)k_fielddiff<KD_FD_SHAPE_S, 1> : (const void*)k_fielddiff<KD_FD_SHAPE_S, 4>)
-                       : (W == 1 ? (const void*)k_fielddiff<KD_FD_SHAPE_L, 1> : (const void*)k_fielddiff<KD_FD_SHAPE_L, 4>);
-    int per_cu = 0;
-    KD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, FD_NT, lds_tab ? o_end : 0));
-    // (the calculator can count one block per CU more than becomes resident: DESIGN.md §3.2)
-#ifndef KD_FD_CAP
-#define KD_FD_CAP 12  // C2 points: 10 / 12 blocks per CU = 36.8 / 35.1 us (C3 is LDS-bound at 8)
-#endif
-    per_cu = std::max(1, std::min(per_cu, walk ? KD_FDW_CAP : stream ? 16 : KD_FD_CAP));
-    const u64 upr = walk ? (u64)FD_NT : stream ? (u64)fd_stream_t<KD_FD_SSHAPE>() : !lds_tab ? FD_NT : small ? fd_upr<KD_FD_SHAPE_S>(nullptr) : fd_upr<KD_FD_SHAPE_L>(nullptr);
-    unsigned blocks = (unsigned)std::min<u64>((work + upr - 1) / upr, (u64)ctx->n_cu * (u64)per_cu);
-    if (blocks == 0) blocks = 1;
-    rc = launch(ctx, "k_fielddiff", [&] {
-        auto args = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(FD_NT), o_end, ctx->stream, (const u8*)d_od, (const u64*)d_ooff,
-                               (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, n_part,
-                               tb, to, (const u8*)dt, d_masks, d_status);
-        };
-        if (walk)
-            hipLaunchKernelGGL((k_fdwalk<KD_FDW_SHAPE>), dim3(blocks), dim3(FD_NT), o_end, ctx->stream, (const u8*)d_od,
-                               (const u64*)d_ooff, (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, n_part,
-                               (u64)ob->n, (u64)nb->n, tb, to, (const u8*)dt, d_masks, d_status);
-        else if (stream)
-            hipLaunchKernelGGL((k_fielddiff_s<KD_FD_SSHAPE, KD_FD_SPF>), dim3(blocks), dim3(FD_NT), o_end, ctx->stream, (const u8*)d_od,
-                               (const u64*)d_ooff, (const u8*)d_nd, (const u64*)d_noff, n_upd, d_n_upd, n_part, tb, to,
-                               (const u8*)dt, d_masks, d_status);
-        else if (!lds_tab)
-            hipLaunchKernelGGL(k_fielddiff_g, dim3(blocks), dim3(FD_NT), 0, ctx->stream, (const u8*)d_od, (const u64*)d_ooff,
-                               (const u8*)d_nd, (const u64*)d_noff, (const uint2*)d_pu, n_upd, d_n_upd, n_part, tb, d_masks,
-                               d_status);
-        // (mask words kept in registers: one for up to 64 union keys, else four)
-        else if (small) W == 1 ? args(k_fielddiff<KD_FD_SHAPE_S, 1>) : args(k_fielddiff<KD_FD_SHAPE_S, 4>);
-        else W == 1 ? args(k_fielddiff<KD_FD_SHAPE_L, 1>) : args(k_fielddiff<KD_FD_SHAPE_L, 4>);
-    });
-    if (rc) return rc;
-    if (out_mem == KD_MEM_HOST) {
-        if ((rc = stage_d2h(ctx, masks, d_masks, n_upd * W * 8)) || (rc = stage_d2h(ctx, status, d_status, n_upd))) return rc;
+    if ((rc = fd_launch(ctx, ob, nb, a))) return rc;  // variant choice and launch
+    if (out_mem == KD_MEM_HOST) {  // copy-back
+        if ((rc = stage_d2h(ctx, masks, a.masks, n_upd * mp->words * 8)) || (rc = stage_d2h(ctx, status, a.status, n_upd))) return rc;
         prof_flush(ctx);
     }
     return KD_OK;
