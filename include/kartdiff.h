@@ -350,7 +350,8 @@ int kd_geom_filter_deltas(kd_ctx* ctx, const kd_geom_head* heads_old, uint64_t n
                           uint8_t* match, uint32_t* keep, uint64_t* n_keep, uint8_t* enc, uint8_t* enc_ok);
 
 /* The exact stage behind the envelope test: Intersects(feature, filter polygon) for the sides the
- * filter left 1 CANDIDATE, decided on the device wherever FP64 can prove the answer.
+ * filter left 1 CANDIDATE, decided on the device: wherever FP64 can prove the answer (the default), or,
+ * with KD_GF_EXACT in flags, for every supported geometry whose coordinates are within range.
  *
  * Filter: closed rings of finite XY doubles (host memory); its region is the even-odd interior of
  * all rings together, boundary included — a valid OGC polygon's or multipolygon's point set.  Up to
@@ -362,22 +363,41 @@ int kd_geom_filter_deltas(kd_ctx* ctx, const kd_geom_head* heads_old, uint64_t n
  * of its own rings, boundary included.  Intersects holds when a vertex of the feature lies in the
  * filter, a segment of the feature meets a boundary segment of the filter, or the feature is areal
  * and the first vertex of a filter ring lies in it.  Every decision is an exact comparison of
- * doubles or the sign of det = (ax-cx)(by-cy) - (ay-cy)(bx-cx) in FP64, which counts only when
+ * doubles or the sign of det = (ax-cx)(by-cy) - (ay-cy)(bx-cx).
+ *
+ * Without KD_GF_EXACT the sign is taken in FP64 and counts only when
  * |det| > (3 + 16 eps) eps (|(ax-cx)(by-cy)| + |(ay-cy)(bx-cx)|), eps = 2^-53, the sum >= 1e-290 and
  * every operand finite.  A witness makes the side 2 MATCHING; no witness and nothing undecided
  * 0 NON_MATCHING; anything else stays 1 for the caller's exact test — every touching configuration
- * (shared vertex, shared edge, point on the boundary) among them.  Type 7 and above, EWKB flag
- * bits, a count that runs past the value and a non-finite coordinate stay 1 as well (counted
- * unsupported).  No byte outside the GPKG value [goff, goff + glen) of the blob is read.
+ * (shared vertex, shared edge, point on the boundary, collinear overlap) among them, and near
+ * misses inside the bound.
+ *
+ * With KD_GF_EXACT a second pass takes the sides the first left 1: the same bound first (what it
+ * certifies keeps its answer), and where it fails the exact sign of det by floating-point expansion
+ * arithmetic (kd_orient2d_exact_batch computes the same on the host).  Touching then is a witness:
+ * a point equal to an edge's end, on a horizontal edge's span, or on an edge by an exactly zero
+ * determinant; two segments whose closed boxes overlap and whose end points are not strictly on
+ * one side of each other; the first vertex of a filter ring on the feature's boundary.  Such a side
+ * is 2, a side without witness 0, and 1 remains only where a determinant has an operand outside the
+ * expansion's range: a non-zero coordinate must satisfy 2^-485 <= |v| < 2^510 (below, the rounding
+ * error of a product of two coordinates would underflow; above, the sum of the six products could
+ * overflow), which degrees and projected metres do by hundreds of binades.  No decision of either
+ * mode contradicts rational arithmetic.  The flag changes nothing for a side the first pass decides.
+ *
+ * In both modes type 7 and above, EWKB flag bits, a count that runs past the value and a non-finite
+ * coordinate stay 1 (counted unsupported).  No byte outside the GPKG value [goff, goff + glen) of
+ * the blob is read.
  *
  * heads / pairs / blobs as in kd_geom_filter_heads, flags & KD_GF_DELTA_HEADS as in
- * kd_geom_filter_deltas (KD_GF_RECT is ignored); NULL heads: KD_EUNSUPPORTED (the geometry is not
+ * kd_geom_filter_deltas, flags & KD_GF_EXACT as above (KD_GF_RECT is ignored); NULL heads: KD_EUNSUPPORTED (the geometry is not
  * located from legends here), the arenas are required.  A side whose code is not 1, or whose head is
  * not KD_GH_GEOM, is left untouched.  match [n * 2] is updated in place, keep [n] / *n_keep are
  * rebuilt in delta order from the codes (either side 1, 2 or 3), stats[4] <- candidate sides decided
- * true, decided false, left undecided, unsupported or malformed.  Host buffers (out_mem, pairs_mem,
+ * true, decided false, left undecided, unsupported or malformed (their sum is the number of candidate
+ * sides in either mode; a side the exact pass decides counts as true or false).  Host buffers (out_mem, pairs_mem,
  * heads_mem, blobs->mem = KD_MEM_HOST), or everything device memory with the delta count read from
  * *d_n on the device (n = capacity; match 2-B, stats 8-B aligned). */
+#define KD_GF_EXACT 0x4u /* kd_geom_refine: decide what FP64 cannot certify in exact arithmetic */
 typedef struct kd_filter_poly {
     const double* xy;         /* [n_vert][2], each ring closed (first vertex == last)          */
     const uint64_t* ring_off; /* [n_ring + 1]: ring r = vertices ring_off[r] .. ring_off[r+1]  */
@@ -387,6 +407,10 @@ int kd_geom_refine(kd_ctx* ctx, const kd_filter_poly* filter, const kd_geom_head
                    const kd_geom_head* heads_new, uint64_t n_new, uint32_t heads_mem, const kd_blobs* old_blobs,
                    const kd_blobs* new_blobs, const uint32_t* pairs, uint64_t n, const uint64_t* d_n, uint32_t pairs_mem,
                    uint32_t flags, uint8_t* match, uint32_t* keep, uint64_t* n_keep, uint64_t* stats, uint32_t out_mem);
+/* The exact orientation behind KD_GF_EXACT on the host (no context, no device): out[i] <- the sign
+ * of det((a - c), (b - c)) for abc[i] = (ax, ay, bx, by, cx, cy): -1, 0 or +1, or 2 when a coordinate
+ * is outside the range above (NaN and infinities included). */
+int kd_orient2d_exact_batch(const double* abc /* [n][6] */, uint64_t n, int8_t* out);
 
 /* -------- writer formatting -------- */
 #define KD_HEX_BYTES 0u    /* bytes.hex(v): lowercase hex of every byte of every blob                */

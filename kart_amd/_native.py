@@ -31,6 +31,7 @@ KD_COMM_ID_BYTES = 128
 KD_GH_GEOM, KD_GH_NULL, KD_GH_FALLBACK = 0, 2, 3
 KD_GF_RECT = 0x1
 KD_GF_DELTA_HEADS = 0x2  # the geometry heads are in delta order (slot d = delta d)
+KD_GF_EXACT = 0x4  # kd_geom_refine: decide what FP64 cannot certify in exact arithmetic
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -266,6 +267,7 @@ SIGNATURES = {
          ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_uint32],
     ),
+    "kd_orient2d_exact_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "kd_shard_cuts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kd_sf_index_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,

@@ -14,7 +14,7 @@
 // |det| > (3 + 16 eps) eps (|(ax-cx)(by-cy)| + |(ay-cy)(bx-cx)|), eps = 2^-53 (Shewchuk's static
 // bound; the library is built with -ffp-contract=off).  A witness gives 2 MATCHING; no witness and
 // nothing undecided 0 NON_MATCHING; anything else — every touching configuration among them — stays
-// 1 CANDIDATE.  Unsupported or malformed WKB (type >= 7, EWKB flags, counts past the value, a
+// 1 CANDIDATE (unless KD_GF_EXACT is set, below).  Unsupported or malformed WKB (type >= 7, EWKB flags, counts past the value, a
 // non-finite coordinate) stays 1 as well.  No byte outside the GPKG value is read.
 //
 // Kernels: k_gr_list sorts the candidate sides into two work lists by their WKB type (each block
@@ -25,9 +25,18 @@
 // over the filter edges of a tile or over the chunk's segments, whichever has more, and a filter
 // edge whose box misses the feature's envelope is skipped before any determinant.  The kept list is
 // then rebuilt from the codes (gf_rekeep).
+//
+// KD_GF_EXACT adds a second pass between the workers and the statistics.  k_gr_points and k_gr_wave
+// are the EXACT = false instantiations of the two worker templates and run as without the flag;
+// k_gr_relist then lists the sides whose code is still 1, and k_gr_points_x / k_gr_wave_x — the
+// EXACT = true instantiations: same walkers, tiles and chunking — decide them with the determinant's
+// exact sign (kd_exact.h) wherever the static bound fails, so that a touching configuration becomes a
+// witness and only an operand outside that header's range guard leaves a side 1.  Their list may be
+// empty: they read its device-side count and return.
 #include <algorithm>
 #include <cmath>
 
+#include "kd_exact.h"
 #include "kd_geom.h"
 
 namespace kd {
@@ -83,46 +92,94 @@ __device__ __forceinline__ void gr_item(const u32* pre, u32 nblk, u32 off, u32 i
 }
 
 // ---- certified predicates ----
-// sign of det((a - c), (b - c)): +1 / -1 when certain, 0 when not
+// EXACT = false: FP64 behind Shewchuk's static bound, "cannot tell" where it fails (the fast
+// kernels).  EXACT = true: the same bound first — whatever it certifies gets the same answer — and
+// the exact sign from kd_exact.h where it fails; "cannot tell" is then left to operands outside that
+// header's range guard.
+constexpr int GR_UNK = KD_ORIENT_RANGE;  // gr_orient<true>: cannot tell
+
+// sign of det((a - c), (b - c)).  EXACT = false: +1 / -1 when certain, 0 when not.  EXACT = true:
+// +1 / -1 / 0 all certain, GR_UNK when not
+template <bool EXACT>
 __device__ __forceinline__ int gr_orient(double ax, double ay, double bx, double by, double cx, double cy) {
     constexpr double eps = 1.1102230246251565e-16;  // 2^-53
     constexpr double K = (3.0 + 16.0 * eps) * eps;
     const double t1 = (ax - cx) * (by - cy), t2 = (ay - cy) * (bx - cx);
     const double det = t1 - t2, s = fabs(t1) + fabs(t2);
-    if (!(s >= 1e-290 && s < __builtin_huge_val())) return 0;  // tiny, overflowed or NaN
-    if (!(fabs(det) > K * s)) return 0;
-    return det > 0 ? 1 : -1;
+    if constexpr (!EXACT) {
+        if (!(s >= 1e-290 && s < __builtin_huge_val())) return 0;  // tiny, overflowed or NaN
+        if (!(fabs(det) > K * s)) return 0;
+        return det > 0 ? 1 : -1;
+    } else {
+        if (s >= 1e-290 && s < __builtin_huge_val() && fabs(det) > K * s) return det > 0 ? 1 : -1;
+        return kd_orient2d_exact(ax, ay, bx, by, cx, cy);
+    }
 }
 
 // one edge (a, b) of a region's boundary against the point (x, y): crossing parity of the ray to
-// the right (par) and "cannot tell" (und).  (a.y > y) != (b.y > y) is exact; a point equal to an end
-// of the edge, or on a horizontal edge, is on the boundary: undecided.
+// the right (par), "cannot tell" (und) and, EXACT only, "on the edge" (on: a witness).
+// (a.y > y) != (b.y > y) is exact; a point equal to an end of the edge, on a horizontal edge's span
+// or (EXACT) with an exact-zero orientation inside the edge's y-range is on the boundary:
+// undecided without EXACT, `on` with it.  The three cases cover every point of the edge, so where no
+// edge reports `on` the point is on none and the half-open parity is right.
+template <bool EXACT>
 __device__ __forceinline__ void gr_pt_edge(double ax, double ay, double bx, double by, double x, double y, u32& par,
-                                           u32& und) {
-    if ((ax == x && ay == y) || (bx == x && by == y)) { und = 1; return; }
+                                           u32& und, u32& on) {
+    if ((ax == x && ay == y) || (bx == x && by == y)) { (EXACT ? on : und) = 1; return; }
     const bool ua = ay > y, ub = by > y;
     if (ua != ub) {
         if (fmax(ax, bx) < x) return;              // wholly to the left: no crossing
         if (fmin(ax, bx) > x) { par ^= 1; return; }  // wholly to the right: one crossing
-        const int o = gr_orient(ax, ay, bx, by, x, y);
-        if (o == 0) und = 1;
-        else par ^= (u32)((o > 0) == ub);  // an upward edge is crossed when the point is to its left
+        const int o = gr_orient<EXACT>(ax, ay, bx, by, x, y);
+        if constexpr (EXACT) {
+            if (o == GR_UNK) und = 1;
+            else if (o == 0) on = 1;
+            else par ^= (u32)((o > 0) == ub);
+        } else {
+            if (o == 0) und = 1;
+            else par ^= (u32)((o > 0) == ub);  // an upward edge is crossed when the point is to its left
+        }
     } else if (ay == y && by == y && x >= fmin(ax, bx) && x <= fmax(ax, bx)) {
-        und = 1;
+        (EXACT ? on : und) = 1;
     }
 }
 
-// segments (a, b) and (c, d): 0 they do not meet, 2 they cross properly, 1 cannot tell
+// segments (a, b) and (c, d): 0 they do not meet, 2 they meet (EXACT = false: cross properly),
+// 1 cannot tell.  EXACT: with the closed boxes overlapping, o1 * o2 <= 0 and o3 * o4 <= 0 means
+// they share a point — collinear segments whose boxes overlap do, an end on the other's line
+// between its ends does — so 1 is left to an operand out of range.
+template <bool EXACT>
 __device__ __forceinline__ int gr_seg(double ax, double ay, double bx, double by, double cx, double cy, double dx,
                                       double dy) {
     if (fmax(ax, bx) < fmin(cx, dx) || fmax(cx, dx) < fmin(ax, bx) || fmax(ay, by) < fmin(cy, dy) ||
         fmax(cy, dy) < fmin(ay, by))
         return 0;
-    const int o1 = gr_orient(ax, ay, bx, by, cx, cy), o2 = gr_orient(ax, ay, bx, by, dx, dy);
-    if (o1 && o1 == o2) return 0;
-    const int o3 = gr_orient(cx, cy, dx, dy, ax, ay), o4 = gr_orient(cx, cy, dx, dy, bx, by);
-    if (o3 && o3 == o4) return 0;
-    return (o1 && o2 && o3 && o4) ? 2 : 1;
+    if constexpr (!EXACT) {
+        const int o1 = gr_orient<false>(ax, ay, bx, by, cx, cy), o2 = gr_orient<false>(ax, ay, bx, by, dx, dy);
+        if (o1 && o1 == o2) return 0;
+        const int o3 = gr_orient<false>(cx, cy, dx, dy, ax, ay), o4 = gr_orient<false>(cx, cy, dx, dy, bx, by);
+        if (o3 && o3 == o4) return 0;
+        return (o1 && o2 && o3 && o4) ? 2 : 1;
+    } else {
+        // (one call site for the four signs: the expansion code is long)
+        int o[2] = {0, 0};
+        bool unk = false;
+#pragma unroll 1
+        for (int k = 0; k < 2; k++) {
+            const double px = k ? cx : ax, py = k ? cy : ay, qx = k ? dx : bx, qy = k ? dy : by;
+            int prod = 1;
+#pragma unroll 1
+            for (int j = 0; j < 2; j++) {
+                const double rx = k ? (j ? bx : ax) : (j ? dx : cx), ry = k ? (j ? by : ay) : (j ? dy : cy);
+                const int v = gr_orient<true>(px, py, qx, qy, rx, ry);
+                if (v == GR_UNK) { unk = true; prod = 0; }
+                else prod *= v;
+            }
+            o[k] = prod;  // o1 * o2, then o3 * o4 (0 with an unknown among them)
+        }
+        if (o[0] > 0 || o[1] > 0) return 0;  // (both signs certain, equal and non-zero)
+        return unk ? 1 : 2;
+    }
 }
 
 // ---- locating and walking the WKB ----
@@ -316,16 +373,63 @@ __global__ __launch_bounds__(256) void k_gr_list(GrArgs a) {
     }
 }
 
-// the outcome counts of every block summed into stats[4] (one block)
+// the sides the fast kernels left 1, listed again for the exact kernels (KD_GF_EXACT): block b reads
+// k_gr_list's block b — its counts from the scanned bcnt — and keeps the sides whose code is still 1
+// in the same slots of list2, counted in bcnt2 (scanned afterwards like bcnt).  Those are the
+// undecided sides and, rarely, sides the fast kernels refused deep in the WKB; the exact kernels
+// refuse the latter again.  The code byte is the status the fast kernels hand over: they write
+// nothing more than without the flag.
+__global__ __launch_bounds__(256) void k_gr_relist(GrArgs a, u32* list2, u32* bcnt2) {
+    __shared__ u32 s_c[2];
+    const int tid = threadIdx.x;
+    const u32 b = blockIdx.x;
+    if (tid < 2) s_c[tid] = 0;
+    __syncthreads();
+    const u32 np = a.bcnt[b + 1] - a.bcnt[b];  // (bcnt[nblk], the first wave prefix, is every point side)
+    const u32 nw = (b + 1 < a.nblk ? a.bcnt[a.nblk + b + 1] : (u32)*a.tot) - a.bcnt[a.nblk + b];
+    const u32* const src = a.list + 2ull * GR_LB * b;
+    u32* const dst = list2 + 2ull * GR_LB * b;
+    if (np <= 2 * GR_LB && nw <= 2 * GR_LB - np) {  // (what k_gr_list can have written)
+        for (u32 i = tid; i < np; i += 256) {
+            const u32 sid = src[i];
+            if (a.match[sid] == 1) dst[atomicAdd(&s_c[0], 1u)] = sid;  // (LDS: the block's own counters)
+        }
+        for (u32 i = tid; i < nw; i += 256) {
+            const u32 sid = src[2 * GR_LB - 1 - i];
+            if (a.match[sid] == 1) dst[2 * GR_LB - 1 - atomicAdd(&s_c[1], 1u)] = sid;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        bcnt2[b] = s_c[0];
+        bcnt2[a.nblk + b] = s_c[1];
+    }
+}
+
+// the outcome counts of every block summed into stats[4] (one block).  EXACT (KD_GF_EXACT): the part
+// slots of the exact kernels follow the others, as many as the fast workers have; the fast kernels'
+// undecided and unsupported sides are then exactly what the exact kernels took and count again under
+// their final outcome, so only the fast kernels' decided counts are read
+template <bool EXACT>
 __global__ __launch_bounds__(1024) void k_gr_stats(GrArgs a) {
     __shared__ unsigned long long s_s[16][4];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const u32 np = a.np_list + a.np_pts + a.np_wave;
     unsigned long long v[4] = {0, 0, 0, 0};
+    if constexpr (!EXACT) {
 #pragma unroll 4
-    for (u32 i = tid; i < np; i += 1024) {
-        const u32x4 x = ((const u32x4*)a.part)[i];
-        v[0] += x.x; v[1] += x.y; v[2] += x.z; v[3] += x.w;
+        for (u32 i = tid; i < np; i += 1024) {
+            const u32x4 x = ((const u32x4*)a.part)[i];
+            v[0] += x.x; v[1] += x.y; v[2] += x.z; v[3] += x.w;
+        }
+    } else {
+#pragma unroll 4
+        for (u32 i = tid; i < np + a.np_pts + a.np_wave; i += 1024) {
+            const u32x4 x = ((const u32x4*)a.part)[i];
+            const bool handed = i >= a.np_list && i < np;
+            v[0] += x.x; v[1] += x.y;
+            if (!handed) { v[2] += x.z; v[3] += x.w; }
+        }
     }
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -368,7 +472,8 @@ __device__ __forceinline__ u32 gr_stage(const GrArgs& a, double (*s_e)[GR_TILE],
 }
 
 // ---- points and small multipoints: one lane per side ----
-__global__ __launch_bounds__(256) void k_gr_points(GrArgs a) {
+template <bool EXACT>
+__global__ __launch_bounds__(256) void k_gr_points_t(GrArgs a) {
     __shared__ double s_e[4][GR_TILE];
     __shared__ u32 s_st[4];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -393,7 +498,7 @@ __global__ __launch_bounds__(256) void k_gr_points(GrArgs a) {
             s = sid & 1;
             bad = gr_locate(a, d, s, w, wlen) <= 0;
         }
-        u64 parm = 0, undm = 0;  // per point of the side: crossing parity, undecided
+        u64 parm = 0, undm = 0, onm = 0;  // per point of the side: crossing parity, undecided, on the boundary (EXACT)
         for (u32 t = 0; t < ntile; t++) {
             const u32 m = gr_stage<256>(a, s_e, t, cur, tid);
             if (!valid || bad) continue;
@@ -406,10 +511,11 @@ __global__ __launch_bounds__(256) void k_gr_points(GrArgs a) {
                 const double x = ld_f64(w + r.off, r.le), y = ld_f64(w + r.off + 8, r.le);
                 if (!gr_finite(x) || !gr_finite(y)) { bad = true; break; }
                 if (x >= a.f0 && x <= a.f1 && y >= a.f2 && y <= a.f3) {  // (outside the envelope: outside)
-                    u32 par = 0, und = 0;
-                    for (u32 e = 0; e < m; e++) gr_pt_edge(s_e[0][e], s_e[1][e], s_e[2][e], s_e[3][e], x, y, par, und);
+                    u32 par = 0, und = 0, on = 0;
+                    for (u32 e = 0; e < m; e++) gr_pt_edge<EXACT>(s_e[0][e], s_e[1][e], s_e[2][e], s_e[3][e], x, y, par, und, on);
                     parm ^= (u64)par << j;
                     undm |= (u64)und << j;
+                    if constexpr (EXACT) onm |= (u64)on << j;
                 }
                 j++;
             }
@@ -419,7 +525,8 @@ __global__ __launch_bounds__(256) void k_gr_points(GrArgs a) {
         if (valid) {
             if (bad) st = 3;
             else {
-                st = (parm & ~undm) ? 0 : undm ? 2 : 1;
+                if constexpr (EXACT) st = (onm | (parm & ~undm)) ? 0 : undm ? 2 : 1;
+                else st = (parm & ~undm) ? 0 : undm ? 2 : 1;
                 if (st != 2) a.match[2 * d + s] = st == 0 ? 2 : 0;
             }
         }
@@ -432,6 +539,9 @@ __global__ __launch_bounds__(256) void k_gr_points(GrArgs a) {
     __syncthreads();
     if (tid < 4) a.part[4 * (a.np_list + blockIdx.x) + tid] = s_st[tid];
 }
+template __global__ void k_gr_points_t<false>(GrArgs);
+// the exact pass over the sides k_gr_relist listed (a.list / a.bcnt / a.tot / a.part are its own)
+template __global__ void k_gr_points_t<true>(GrArgs);
 
 // ---- lineal and areal geometries (and large multipoints): one wave per side ----
 __device__ __forceinline__ double gr_min64(double v) {
@@ -461,7 +571,8 @@ __device__ __forceinline__ void gr_chunk(const u8* w, const GrRun& r, u32 s0, u3
 
 constexpr int GR_WPB = 4;  // waves per block, each working alone (no block barrier in the kernel)
 constexpr u32 GR_RC = 4;   // runs of a geometry remembered from the first walk (most have one or two)
-__global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
+template <bool EXACT>
+__global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave_t(GrArgs a) {
     __shared__ double s_ew[GR_WPB][4][GR_TILE];
     __shared__ double s_vw[GR_WPB][2][64];
     __shared__ u32 s_rw[GR_WPB][GR_RC][6];
@@ -549,7 +660,7 @@ __global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
                                         if (fmax(ax, bx) < mnx || fmin(ax, bx) > mxx || fmax(ay, by) < mny || fmin(ay, by) > mxy)
                                             continue;
                                         for (u32 j = 0; j < ns; j++) {
-                                            const int q = gr_seg(ax, ay, bx, by, s_vx[j], s_vy[j], s_vx[j + 1], s_vy[j + 1]);
+                                            const int q = gr_seg<EXACT>(ax, ay, bx, by, s_vx[j], s_vy[j], s_vx[j + 1], s_vy[j + 1]);
                                             lw |= q == 2;
                                             lu |= q == 1;
                                         }
@@ -560,7 +671,7 @@ __global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
                                         const double ax = s_e[0][e], ay = s_e[1][e], bx = s_e[2][e], by = s_e[3][e];
                                         if (fmax(ax, bx) < mnx || fmin(ax, bx) > mxx || fmax(ay, by) < mny || fmin(ay, by) > mxy)
                                             continue;
-                                        const int q = gr_seg(ax, ay, bx, by, cx, cy, dx, dy);
+                                        const int q = gr_seg<EXACT>(ax, ay, bx, by, cx, cy, dx, dy);
                                         lw |= q == 2;
                                         lu |= q == 1;
                                     }
@@ -581,12 +692,13 @@ __global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
                             const u8* p = w + r.off + (u64)i * r.stride;
                             const double x = ld_f64(p, r.le), y = ld_f64(p + 8, r.le);
                             if (!(x >= a.f0 && x <= a.f1 && y >= a.f2 && y <= a.f3)) continue;
-                            u32 par = 0, pu = 0;
+                            u32 par = 0, pu = 0, on = 0;
                             for (u32 t = 0; t < ntile; t++) {
                                 const u32 m = gr_stage<64>(a, s_e, t, cur, lane);
-                                for (u32 e = lane; e < m; e += 64) gr_pt_edge(s_e[0][e], s_e[1][e], s_e[2][e], s_e[3][e], x, y, par, pu);
+                                for (u32 e = lane; e < m; e += 64) gr_pt_edge<EXACT>(s_e[0][e], s_e[1][e], s_e[2][e], s_e[3][e], x, y, par, pu, on);
                             }
-                            if (__any(pu)) und = true;
+                            if (EXACT && __any(on)) wit = true;  // (on the boundary: certain whatever else is not)
+                            else if (__any(pu)) und = true;
                             else if (__popcll(__ballot(par)) & 1) wit = true;
                         }
                     }
@@ -597,11 +709,12 @@ __global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
                         const double qx = a.fe[4ull * a.nep + rq], qy = a.fe[4ull * a.nep + a.nr + rq];
                         if (!(qx >= mnx && qx <= mxx && qy >= mny && qy <= mxy)) continue;
                         rewind();
-                        u32 par = 0, pu = 0, poly = 0xFFFFFFFFu;
+                        u32 par = 0, pu = 0, on = 0, poly = 0xFFFFFFFFu;
                         auto fin = [&] {
-                            if (__any(pu)) und = true;
+                            if (EXACT && __any(on)) wit = true;  // (the ring's first vertex on F's boundary)
+                            else if (__any(pu)) und = true;
                             else if (__popcll(__ballot(par)) & 1) wit = true;
-                            par = pu = 0;
+                            par = pu = on = 0;
                         };
                         while (next()) {
                             if (r.poly != poly) {
@@ -612,7 +725,7 @@ __global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
                             for (u32 s0 = 0; s0 < r.cnt; s0 += GR_CH) {
                                 const u32 ns = min((u32)GR_CH, r.cnt - s0);
                                 gr_chunk(w, r, s0, ns, s_vx, s_vy, lane);
-                                if ((u32)lane < ns) gr_pt_edge(s_vx[lane], s_vy[lane], s_vx[lane + 1], s_vy[lane + 1], qx, qy, par, pu);
+                                if ((u32)lane < ns) gr_pt_edge<EXACT>(s_vx[lane], s_vy[lane], s_vx[lane + 1], s_vy[lane + 1], qx, qy, par, pu, on);
                             }
                         }
                         if (poly != 0xFFFFFFFFu && !wit) fin();
@@ -627,6 +740,8 @@ __global__ __launch_bounds__(64 * GR_WPB) void k_gr_wave(GrArgs a) {
     }
     if (lane < 4) a.part[4 * (a.np_list + a.np_pts + blockIdx.x * GR_WPB + wid) + lane] = lane == 0 ? cst[0] : lane == 1 ? cst[1] : lane == 2 ? cst[2] : cst[3];
 }
+template __global__ void k_gr_wave_t<false>(GrArgs);
+template __global__ void k_gr_wave_t<true>(GrArgs);
 
 // FNV-1a over the filter's bytes (the key of its device copy)
 static u64 gr_hash(const void* p, size_t n, u64 h) {
@@ -698,6 +813,15 @@ static int gr_filter(kd_ctx* ctx, const kd_filter_poly* f, GrArgs& a) {
 
 using namespace kd;
 
+extern "C" int kd_orient2d_exact_batch(const double* abc, uint64_t n, int8_t* out) {
+    KD_CHECK(n == 0 || (abc && out), "kd_orient2d_exact_batch: NULL argument");
+    for (u64 i = 0; i < n; i++) {
+        const double* p = abc + 6 * i;
+        out[i] = (int8_t)kd_orient2d_exact(p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+    return KD_OK;
+}
+
 extern "C" int kd_geom_refine(kd_ctx* ctx, const kd_filter_poly* filter, const kd_geom_head* heads_old, uint64_t n_old,
                               const kd_geom_head* heads_new, uint64_t n_new, uint32_t heads_mem, const kd_blobs* old_blobs,
                               const kd_blobs* new_blobs, const uint32_t* pairs, uint64_t n, const uint64_t* d_n,
@@ -719,7 +843,7 @@ extern "C" int kd_geom_refine(kd_ctx* ctx, const kd_filter_poly* filter, const k
     GrArgs a{};
     if ((rc = gr_filter(ctx, filter, a))) return rc;
     const bool host_out = out_mem == KD_MEM_HOST;
-    // the scan's total (u64) at 0, stats[4] (u64) at 16
+    // the scan's total (u64) at 0, stats[4] (u64) at 16, the second scan's total (u64) at 48
     void* dc;
     if ((rc = ensure(ctx, "gr.cnt", 64, &dc))) return rc;
     unsigned long long* dstats = host_out ? (unsigned long long*)((char*)dc + 16) : (unsigned long long*)stats;
@@ -780,11 +904,17 @@ extern "C" int kd_geom_refine(kd_ctx* ctx, const kd_filter_poly* filter, const k
     const u64 cu = (u64)ctx->n_cu;
     const u64 nblk = (n + GR_LB - 1) / GR_LB;
     const unsigned g_pts = (unsigned)std::max<u64>(1, std::min<u64>((2 * n + 255) / 256, cu * 4));
-    const int occ = occupancy(ctx, (const void*)k_gr_wave, 64 * GR_WPB, 0);
+    const int occ = occupancy(ctx, (const void*)k_gr_wave_t<false>, 64 * GR_WPB, 0);
     const unsigned g_wave = (unsigned)std::max<u64>(1, std::min<u64>((2 * n + GR_WPB - 1) / GR_WPB, cu * (u64)occ));
+    // KD_GF_EXACT: a second pass over the sides the fast kernels leave 1, with a work list, block
+    // counts and part slots of its own behind theirs; the same grids (a block whose share of the
+    // list is empty — every block when nothing was left — reads the device-side count and returns)
+    const bool exact = (flags & KD_GF_EXACT) != 0;
+    const u64 np_x = exact ? g_pts + (u64)g_wave * GR_WPB : 0;
     void *dl, *db, *dpart;
-    if ((rc = ensure(ctx, "gr.list", 8 * GR_LB * nblk, &dl)) || (rc = ensure(ctx, "gr.bcnt", 8 * nblk + 16, &db)) ||
-        (rc = ensure(ctx, "gr.part", 16 * (nblk + g_pts + (u64)g_wave * GR_WPB), &dpart)))
+    if ((rc = ensure(ctx, "gr.list", 8 * GR_LB * nblk * (exact ? 2 : 1), &dl)) ||
+        (rc = ensure(ctx, "gr.bcnt", (8 * nblk + 16) * (exact ? 2 : 1), &db)) ||
+        (rc = ensure(ctx, "gr.part", 16 * (nblk + g_pts + (u64)g_wave * GR_WPB + np_x), &dpart)))
         return rc;
     a.list = (u32*)dl;
     a.bcnt = (u32*)db;
@@ -798,11 +928,30 @@ extern "C" int kd_geom_refine(kd_ctx* ctx, const kd_filter_poly* filter, const k
     if ((rc = launch(ctx, "k_gr_list", [&] { hipLaunchKernelGGL(k_gr_list, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, a); })))
         return rc;
     if ((rc = gf_scan(ctx, (u32*)db, (u32)(2 * nblk), (u64*)dc))) return rc;
-    if ((rc = launch(ctx, "k_gr_points", [&] { hipLaunchKernelGGL(k_gr_points, dim3(g_pts), dim3(256), 0, ctx->stream, a); })))
+    if ((rc = launch(ctx, "k_gr_points", [&] { hipLaunchKernelGGL(k_gr_points_t<false>, dim3(g_pts), dim3(256), 0, ctx->stream, a); })))
         return rc;
-    if ((rc = launch(ctx, "k_gr_wave", [&] { hipLaunchKernelGGL(k_gr_wave, dim3(g_wave), dim3(64 * GR_WPB), 0, ctx->stream, a); })))
+    if ((rc = launch(ctx, "k_gr_wave", [&] { hipLaunchKernelGGL(k_gr_wave_t<false>, dim3(g_wave), dim3(64 * GR_WPB), 0, ctx->stream, a); })))
         return rc;
-    if ((rc = launch(ctx, "k_gr_stats", [&] { hipLaunchKernelGGL(k_gr_stats, dim3(1), dim3(1024), 0, ctx->stream, a); })))
+    if (exact) {
+        GrArgs x = a;
+        x.list = a.list + 2 * GR_LB * nblk;
+        x.bcnt = a.bcnt + 2 * nblk + 4;
+        x.tot = (const u64*)((char*)dc + 48);
+        x.part = a.part + 4 * ((u64)a.np_pts + a.np_wave);  // (its workers' slots follow the fast ones)
+        if ((rc = launch(ctx, "k_gr_relist", [&] {
+                 hipLaunchKernelGGL(k_gr_relist, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, a, x.list, x.bcnt);
+             })))
+            return rc;
+        if ((rc = gf_scan(ctx, x.bcnt, (u32)(2 * nblk), (u64*)((char*)dc + 48)))) return rc;
+        if ((rc = launch(ctx, "k_gr_points_x", [&] { hipLaunchKernelGGL(k_gr_points_t<true>, dim3(g_pts), dim3(256), 0, ctx->stream, x); })))
+            return rc;
+        if ((rc = launch(ctx, "k_gr_wave_x", [&] { hipLaunchKernelGGL(k_gr_wave_t<true>, dim3(g_wave), dim3(64 * GR_WPB), 0, ctx->stream, x); })))
+            return rc;
+    }
+    if ((rc = launch(ctx, "k_gr_stats", [&] {
+             if (exact) hipLaunchKernelGGL(k_gr_stats<true>, dim3(1), dim3(1024), 0, ctx->stream, a);
+             else hipLaunchKernelGGL(k_gr_stats<false>, dim3(1), dim3(1024), 0, ctx->stream, a);
+         })))
         return rc;
     if ((rc = gf_rekeep(ctx, dm, n, d_n, dk, nk_dst))) return rc;
     if (!host_out) return KD_OK;

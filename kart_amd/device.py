@@ -457,7 +457,7 @@ class FilterPipeline:
     whole layer in one stream."""
 
     def __init__(self, engine, base, target, base_blobs, target_blobs, geom_cols, filt_env, rectangle=False, bits=20,
-                 heads=False, delta_order=False, gather=False, polygons=None):
+                 heads=False, delta_order=False, gather=False, polygons=None, exact=False):
         """heads: filter from 48-B geometry heads (the blob reader's host pass) instead of the blob
         arenas; delta_order (with heads): the heads in delta order, as the drop-in's blob reader lays
         them out after classification (it reads the deltas' blobs) — built once on the host from the
@@ -468,7 +468,9 @@ class FilterPipeline:
         polygons (needs heads): the filter geometry's rings ([polygon][ring][(x, y)], or a SpatialFilter
         that carries them) — every step then decides its candidate sides against them on the device
         (kd_geom_refine) behind the envelope filter; ``results()`` keeps its shape, ``refine_stats()``
-        gives the last step's counters"""
+        gives the last step's counters;
+        exact (with polygons): the refine also decides what FP64 cannot certify — touching
+        configurations — in exact arithmetic on the device (KD_GF_EXACT)"""
         import ctypes as _c
 
         if polygons is not None and not heads:
@@ -503,6 +505,7 @@ class FilterPipeline:
         self.dheads = None
         self.delta_heads_s = None
         self._poly = None
+        self.exact = bool(exact)
         if polygons is not None:
             from .spatial import SpatialFilter
 
@@ -600,7 +603,8 @@ class FilterPipeline:
         L, ctx = self.eng.L, self.eng.ctx
         N.check(L.kd_geom_refine(ctx, ctypes.byref(self._poly), ho.ptr, no, hn.ptr, nn, N.KD_MEM_DEVICE,
                                  ctypes.byref(self._ob), ctypes.byref(self._nb), self.delta.ptr, self.cap,
-                                 self.counts.ptr + 24, N.KD_MEM_DEVICE, flags, self.match.ptr, self.keep.ptr,
+                                 self.counts.ptr + 24, N.KD_MEM_DEVICE, flags | (N.KD_GF_EXACT if self.exact else 0),
+                                 self.match.ptr, self.keep.ptr,
                                  self.n_keep.ptr, self.rstats.ptr, N.KD_MEM_DEVICE), "kd_geom_refine")
 
     def refine_stats(self):

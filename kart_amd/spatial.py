@@ -16,7 +16,9 @@
   POLYGON and MULTIPOLYGON filters, kart/spatial_filter/__init__.py:261) and is no rectangle has its
   candidates decided on the GPU too (``kd_geom_refine``: Intersects wherever FP64 certifies the
   answer); what stays a candidate after that — touching configurations, unsupported WKB — follows
-  the host path as before.
+  the host path as before.  With ``exact=True`` on the filter the touching configurations are
+  decided on the GPU as well (``KD_GF_EXACT``: the determinant's exact sign where FP64 cannot
+  certify it), and only unsupported WKB is left to the host.
 """
 import ctypes
 import re
@@ -103,15 +105,18 @@ def gpkg_envelope_2d(g):
 class SpatialFilter:
     """A spatial filter in a dataset's CRS: ``filter_env`` (min-x, max-x, min-y, max-y) of the filter
     geometry, the dataset's geometry column, and the exact test ``intersects(gpkg_bytes) -> bool``
-    (the prepared filter geometry's Intersects; optional)."""
+    (the prepared filter geometry's Intersects; optional).  ``exact``: a filter that carries its
+    polygons has every supported candidate decided on the GPU in exact arithmetic (KD_GF_EXACT),
+    touching configurations included; off by default."""
 
     def __init__(self, filter_env=None, geom_column_name=None, intersects=None, rectangle=False, match_all=False,
-                 polygons=None):
+                 polygons=None, exact=False):
         self.match_all = match_all
         self.filter_env = None if match_all else tuple(float(x) for x in filter_env)
         self.geom_column_name = geom_column_name
         self.intersects = intersects
         self.rectangle = bool(rectangle)
+        self.exact = bool(exact)
         # the filter geometry itself: [polygon][ring][(x, y)], every ring closed (None: envelope only)
         self.polygons = _closed_polygons(polygons) if polygons is not None else None
         self._poly_arrays = None
@@ -124,15 +129,15 @@ class SpatialFilter:
         return cls((min_x, max_x, min_y, max_y), geom_column_name, rectangle=True)
 
     @classmethod
-    def from_ring(cls, ring, geom_column_name=None, intersects=None):
+    def from_ring(cls, ring, geom_column_name=None, intersects=None, exact=False):
         """a polygon filter from its exterior ring [(x, y), ...]; a point's Intersects is tested
         exactly (point in polygon, boundary included), other geometries need ``intersects``"""
         env, rect = _ring_env_rect(ring)
         return cls(env, geom_column_name, intersects=intersects or _ring_point_test(ring), rectangle=rect,
-                   polygons=[[ring]])
+                   polygons=[[ring]], exact=exact)
 
     @classmethod
-    def from_polygons(cls, polygons, geom_column_name=None, intersects=None):
+    def from_polygons(cls, polygons, geom_column_name=None, intersects=None, exact=False):
         """a polygon or multipolygon filter: ``polygons`` = [polygon], polygon = [ring] (exterior
         first, then holes), ring = [(x, y), ...] (closed here if it is not).  The filter's region is
         the even-odd interior of all rings, boundary included.  ``rectangle`` by from_ring's rule (one
@@ -144,13 +149,13 @@ class SpatialFilter:
         xs, ys = [p[0] for p in pts], [p[1] for p in pts]
         env = (min(xs), max(xs), min(ys), max(ys))
         rect = len(polys) == 1 and len(polys[0]) == 1 and _ring_env_rect(polys[0][0])[1]
-        return cls(env, geom_column_name, intersects=intersects, rectangle=rect, polygons=polys)
+        return cls(env, geom_column_name, intersects=intersects, rectangle=rect, polygons=polys, exact=exact)
 
     @classmethod
-    def from_wkt(cls, text, geom_column_name=None, intersects=None):
+    def from_wkt(cls, text, geom_column_name=None, intersects=None, exact=False):
         """from POLYGON(...) / MULTIPOLYGON(...) WKT — the only types the reference accepts as a
         spatial filter (kart/spatial_filter/__init__.py:261); Z / M ordinates are dropped"""
-        return cls.from_polygons(parse_polygon_wkt(text), geom_column_name, intersects)
+        return cls.from_polygons(parse_polygon_wkt(text), geom_column_name, intersects, exact)
 
     def polygon_arrays(self):
         """(xy float64 [n_vert, 2], ring_off uint64 [n_ring + 1]) of the filter's rings — kd_filter_poly;
@@ -171,7 +176,7 @@ class SpatialFilter:
         cols = [c for c in schema.columns if c.data_type == "geometry"]
         if not cols:
             return SpatialFilter.MATCH_ALL
-        out = SpatialFilter(self.filter_env, cols[0].name, self.intersects, self.rectangle)
+        out = SpatialFilter(self.filter_env, cols[0].name, self.intersects, self.rectangle, exact=self.exact)
         out.polygons = self.polygons
         if self.polygons is not None:
             out._poly_arrays = self.polygon_arrays()
@@ -445,9 +450,11 @@ def geom_filter_heads(engine, old_heads, new_heads, pairs, filt_env, rectangle=F
     return match[:n], keep[:k], (enc[:n] if bits else None), (ok[:n] if bits else None)
 
 
-def geom_refine(engine, polygon_arrays, old_heads, new_heads, pairs, codes, arenas, delta_heads=False):
+def geom_refine(engine, polygon_arrays, old_heads, new_heads, pairs, codes, arenas, delta_heads=False, exact=False):
     """kd_geom_refine over host buffers: the sides ``codes`` has as 1 (CANDIDATE) decided against the
-    filter polygon where FP64 certifies Intersects.  ``polygon_arrays`` = (xy [n_vert, 2], ring_off
+    filter polygon where FP64 certifies Intersects — with ``exact`` (KD_GF_EXACT) wherever the
+    geometry is supported and its coordinates within the exact predicate's range, touching
+    configurations included.  ``polygon_arrays`` = (xy [n_vert, 2], ring_off
     [n_ring + 1]) (SpatialFilter.polygon_arrays); heads, pairs, ``arenas`` ((od, oo), (nd, no)) and
     ``delta_heads`` as in geom_filter_heads.  Returns (codes uint8 [n, 2], keep uint32 [k], stats):
     stats = candidate sides decided true / false, left undecided, unsupported or malformed."""
@@ -477,7 +484,8 @@ def geom_refine(engine, polygon_arrays, old_heads, new_heads, pairs, codes, aren
     N.check(engine.L.kd_geom_refine(
         engine.ctx, ctypes.byref(fp), hs[0].ctypes.data if hs[0].size else None, hs[0].shape[0],
         hs[1].ctypes.data if hs[1].size else None, hs[1].shape[0], N.KD_MEM_HOST, ctypes.byref(blobs[0]),
-        ctypes.byref(blobs[1]), N.ptr(pairs), n, None, N.KD_MEM_HOST, N.KD_GF_DELTA_HEADS if delta_heads else 0,
+        ctypes.byref(blobs[1]), N.ptr(pairs), n, None, N.KD_MEM_HOST,
+        (N.KD_GF_DELTA_HEADS if delta_heads else 0) | (N.KD_GF_EXACT if exact else 0),
         N.ptr(match), N.ptr(keep), ctypes.byref(nk), N.ptr(st), N.KD_MEM_HOST), "kd_geom_refine")
     stats = {"true": int(st[0]), "false": int(st[1]), "undecided": int(st[2]), "unsupported": int(st[3])}
     return match[:n], keep[:int(nk.value)], stats
@@ -550,9 +558,10 @@ def filtered_ds_feature_deltas(engine, ds_diff, old_version, new_version, spatia
     psf = old_sf if not old_sf.match_all else new_sf
     if psf.polygons and not rect:
         # the exact stage: candidates decided against the filter's rings on the GPU; what it cannot
-        # certify (touching configurations, unsupported WKB) stays a candidate for _resolve
+        # certify (touching configurations unless psf.exact, unsupported WKB) stays a candidate for
+        # _resolve
         codes, keep, rst = geom_refine(engine, psf.polygon_arrays(), dense[0], dense[1], pairs, codes, sides,
-                                       delta_heads=True)
+                                       delta_heads=True, exact=psf.exact)
         acc = spatial_filter.stats.setdefault("refine", {})
         for k, v in rst.items():
             acc[k] = acc.get(k, 0) + v
