@@ -9,6 +9,10 @@
  *   kd_fielddiff   <- Dataset3.get_feature (kart/dataset3.py:185-223) + Schema.feature_from_raw_dict
  *                     (kart/schema.py:288-293) + the per-field Python `==` compare of
  *                     TextDiffWriter.write_feature_delta (kart/text_diff_writer.py:135-145).
+ *   kd_find_renames <- WorkingCopy.find_renames (kart/working_copy/base.py:829-854) for a commit<>commit
+ *                     diff, the TODO at kart/rich_base_dataset.py:233: deletes and inserts whose blob
+ *                     OIDs are equal (Schema.hash_feature(.., without_pk=True), kart/schema.py:314-335)
+ *                     paired on the GPU, at any size (the reference caps its pass at 400 deltas, :688).
  *   kd_merge3      <- repo.merge_trees(ancestor, ours, theirs) (kart/merge.py:99-100; libgit2
  *                     git_merge_trees) feeding MergeIndex.from_pygit2_index (kart/merge_util.py:92-103).
  *   kd_envelopes   <- SpatialFilter.matches envelope quick-check (kart/spatial_filter/__init__.py:534-590,
@@ -226,6 +230,37 @@ int kd_diff2_device_ex(kd_ctx* ctx, const kd_side* base, const kd_side* target, 
 int kd_fielddiff(kd_ctx* ctx, const kd_blobs* old_blobs, const kd_blobs* new_blobs,
                  const uint32_t* pu, uint64_t n_upd, const uint64_t* d_n_upd, uint32_t pairs_mem,
                  const kd_legend_maps* maps, uint64_t* masks, uint8_t* status, uint32_t out_mem);
+
+/* -------- renames: deletes and inserts paired by blob OID -------- */
+/* <- WorkingCopy.find_renames (kart/working_copy/base.py:829-854) for a commit<>commit diff, the TODO
+ * at kart/rich_base_dataset.py:233: blob OID == Schema.hash_feature(.., without_pk=True)
+ * (kart/schema.py:314-335; a V3 feature blob is msg_pack([legend hash, non-pk values]), the pk lives in
+ * the path: kart/dataset3.py:261-272), for features stored under the current legend.
+ *
+ * delta [n_delta] = the (base index | KD_NONE, target index | KD_NONE) records of a two-way diff in its
+ * key order.  A delete has only a base index, an insert only a target index; updates, and records whose
+ * index lies outside its side, are ignored.  For every OID (all 20 bytes) that occurs on at least one
+ * delete and at least one insert, the delete with the largest delta index is paired with the insert
+ * with the largest delta index (the reference's two dicts, filled in iteration order); every other
+ * delta of that OID stays.  ren[k] = (delta index of the delete, delta index of the insert), ascending
+ * by the delete's delta index; *n_ren = the number of pairs.  A pure function of the inputs, bitwise
+ * reproducible.  A caller diffing in reverse swaps the pair columns: the pairing is symmetric.
+ *
+ * Only n, oid and mem of the sides are read (oid 4-byte aligned).  base_order / target_order (both or
+ * NULL, in the memory of their side) as kd_diff2_device_perm: the OID of sorted entry i is
+ * oid[order[i]].  list_mem / out_mem say where delta and ren / n_ren live; host lists and outputs are
+ * staged by the library (the call then returns with the results).  With d_n_delta != NULL the count is
+ * read on the device, n_delta is the capacity (it sizes the grid and the workspace), delta, ren and
+ * n_ren must be device memory and the call is asynchronous; no record beyond the device count
+ * influences the result.  ren needs room for min(deletes, inserts) pairs (n_delta / 2 always does).
+ * Workspace (grow-only, kept by the context): 20 bytes per delta of n_delta for the lists and a
+ * table of 16 bytes times the power of two at or above 2 * min(n_delta, base->n), so pass the
+ * tightest n_delta the caller knows.
+ * KD_EINVAL: NULL where a pointer is required, one order without the other, n_delta > 2^32 - 2. */
+int kd_find_renames(kd_ctx* ctx, const kd_side* base, const kd_side* target,
+                    const uint32_t* base_order, const uint32_t* target_order,
+                    const uint32_t* delta, uint64_t n_delta, const uint64_t* d_n_delta, uint32_t list_mem,
+                    uint32_t* ren, uint64_t* n_ren, uint32_t out_mem);
 
 /* -------- three-way merge classification -------- */
 int kd_merge3(kd_ctx* ctx, const kd_side* ancestor, const kd_side* ours, const kd_side* theirs,

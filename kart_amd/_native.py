@@ -219,6 +219,12 @@ SIGNATURES = {
          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(KdLegendMaps),
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32],
     ),
+    "kd_find_renames": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(KdSide), ctypes.POINTER(KdSide), ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_uint32],
+    ),
     "kd_merge3": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.POINTER(KdSide), ctypes.POINTER(KdSide), ctypes.POINTER(KdSide),

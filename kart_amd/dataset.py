@@ -293,13 +293,14 @@ class UpdateBatch:
     walking the DeltaDiff or touching a blob object.  ``prefetch``: a future of those two arenas,
     read while the deltas were being built (or None)"""
 
-    __slots__ = ("old_v", "new_v", "old_leaf", "new_leaf", "deltas", "keys", "n_total", "prefetch")
+    __slots__ = ("old_v", "new_v", "old_leaf", "new_leaf", "deltas", "keys", "n_total", "prefetch", "renamed")
 
     def __init__(self):
         self.old_v = self.new_v = None
         self.old_leaf = self.new_leaf = None
         self.deltas, self.keys, self.n_total = [], [], -1
         self.prefetch = None
+        self.renamed = []  # find_renames: the folded deltas (old key != new key, one blob): no kernel work
 
 
 # diffs with at least this many updates read the updates' blobs while their deltas are built
@@ -359,8 +360,51 @@ def _start_prefetch(old_v, new_v, old_leaf, new_leaf):
     return _Prefetch(old_v, new_v, np.asarray(old_leaf, np.int64), np.asarray(new_leaf, np.int64))
 
 
-def diff_feature(engine, base, target, feature_filter=None, reverse=False, updates=None, _collect=None):
+def can_find_renames(meta_diff):
+    """WorkingCopy.can_find_renames (kart/working_copy/base.py:812-827): no schema.json change, or the
+    two schemas differ by type updates only — the same column ids in the same positions with the same
+    names and primary-key indices (Schema.diff_type_counts, kart/schema.py:451-495)"""
+    if "schema.json" not in meta_diff:
+        return True
+    d = meta_diff["schema.json"]
+    old, new = d.old_value, d.new_value
+    if not old or not new:
+        return False
+
+    def shape(cols):
+        return [(c["id"], c["name"], c.get("primaryKeyIndex")) for c in cols]
+
+    return shape(old) == shape(new)
+
+
+def _rename_pairs(engine, A, B, delta, reverse, kept=None):
+    """(delete row, insert row) of the deltas find_renames folds, as rows of ``delta`` in the caller's
+    (possibly reversed) view: the engine pairs the kept records, a reversed diff swaps the columns"""
+    sub = delta if kept is None else np.ascontiguousarray(delta[kept])
+    ren = np.asarray(engine.find_renames(A, B, sub), np.int64).reshape(-1, 2)
+    if kept is not None:
+        ren = kept[ren]
+    return ren[:, ::-1] if reverse else ren
+
+
+def _fold_renames(ren, get):
+    """{delete row: folded delta or None}, set of the rows it replaces: delete_delta + insert_delta by
+    the structures' own algebra (Delta.maybe_update(old, new), flags kept: kart/diff_structs.py:142-180)"""
+    folded, gone = {}, set()
+    for di, ii in ren.tolist():
+        folded[di] = get(di) + get(ii)
+        gone.add(ii)
+    return folded, gone
+
+
+def diff_feature(engine, base, target, feature_filter=None, reverse=False, updates=None, _collect=None,
+                 find_renames=False):
     """Generator of Delta with lazy values (RichBaseDataset.diff_feature semantics).
+
+    find_renames: a delete and an insert of one blob OID (a feature re-keyed, values untouched) fold
+    into one update delta with old key != new key, at most one pair per OID — WorkingCopy.find_renames
+    (kart/working_copy/base.py:829-854) at the TODO of kart/rich_base_dataset.py:233, paired on the
+    GPU.  The folded delta takes the delete's place, the insert is dropped.
 
     base / target: DatasetVersion or None (a missing dataset diffs against the empty tree).
     updates: an UpdateBatch that receives the yielded update deltas (set once the generator is
@@ -379,6 +423,12 @@ def diff_feature(engine, base, target, feature_filter=None, reverse=False, updat
     t = _lap("classify2", t)
     old_v, new_v = (target, base) if reverse else (base, target)
     d = res.delta
+    match_all = feature_filter is None or getattr(feature_filter, "match_all", False)
+    ren = None  # (delete row, insert row) of the pairs to fold
+    if find_renames and base is not None and target is not None and res.n_insert and res.n_delete and match_all:
+        ren = _rename_pairs(engine, A, B, d, reverse)
+        t = _lap("find_renames", t)
+    sides = (A, B)
     if reverse:
         d = d[:, ::-1]
         A, B = B, A
@@ -390,7 +440,6 @@ def diff_feature(engine, base, target, feature_filter=None, reverse=False, updat
     new_leaf = np.full(n, -1, np.int64)
     old_leaf[ia] = A.order[a_idx[ia]]
     new_leaf[ib] = B.order[b_idx[ib]]
-    match_all = feature_filter is None or getattr(feature_filter, "match_all", False)
     if updates is not None and match_all and old_v is not None and new_v is not None:
         # the updates' blobs are read on a worker thread (native, GIL released) while the deltas
         # are built here: field_diff then takes the arenas from updates.prefetch
@@ -414,6 +463,22 @@ def diff_feature(engine, base, target, feature_filter=None, reverse=False, updat
             old_leaf, new_leaf, old_pks, new_pks, own, _collect)
         n_total = len(dl)
         t = _lap("build_deltas", t)
+        renamed = []
+        if ren is not None and ren.shape[0]:
+            folded, gone = _fold_renames(ren, dl.__getitem__)
+            for di, f in folded.items():
+                if f is None:
+                    gone.add(di)
+                elif _collect is not None:
+                    _collect[keys[di]] = f  # (delta.key: the old key, the delete's own place)
+            if _collect is not None:
+                for i in gone:
+                    del _collect[keys[i]]
+            else:
+                dl = [folded.get(i, x) for i, x in enumerate(dl) if i not in gone]
+            renamed = [f for f in folded.values() if f is not None]
+            n_total -= len(gone)
+            t = _lap("fold_renames", t)
         if _collect is None:
             yield from dl
     else:
@@ -422,6 +487,16 @@ def diff_feature(engine, base, target, feature_filter=None, reverse=False, updat
         if isinstance(new_pks, np.ndarray):
             new_pks = new_pks.tolist()
         upd_rows, upd_deltas, upd_keys, n_total = [], [], [], 0
+        renamed = []
+        hold = None  # find_renames: row -> delta, folded and handed on after the loop
+        if find_renames and not match_all and base is not None and target is not None:
+            # the reference pairs what the filter left: the engine pairs the kept records only
+            kept = np.asarray([i for i in range(n) if (old_leaf[i] >= 0 and str(old_pks[i]) in feature_filter) or
+                               (new_leaf[i] >= 0 and str(new_pks[i]) in feature_filter)], np.int64)
+            if kept.size:
+                ren = _rename_pairs(engine, sides[0], sides[1], res.delta, reverse, kept)
+        if ren is not None and ren.shape[0]:
+            hold = {}
         store = _collect.__setitem__ if _collect is not None else None
         Delta, KeyValue, new_obj, partial = _deltas.Delta, _deltas.KeyValue, object.__new__, functools.partial
         olist, nlist = old_leaf.tolist(), new_leaf.tolist()
@@ -447,16 +522,32 @@ def diff_feature(engine, base, target, feature_filter=None, reverse=False, updat
                 upd_deltas.append(delta)
                 upd_keys.append(opk)
             n_total += 1
-            if _collect is None:
+            if hold is not None:
+                hold[i] = delta
+            elif _collect is None:
                 yield delta
             else:
                 store(opk if ob is not None else npk, delta)
+        if hold is not None:
+            folded, gone = _fold_renames(ren, hold.__getitem__)
+            gone.update(di for di, f in folded.items() if f is None)
+            renamed = [f for f in folded.values() if f is not None]
+            n_total -= len(gone)
+            for i, delta in hold.items():
+                if i in gone:
+                    continue
+                delta = folded.get(i, delta)
+                if _collect is None:
+                    yield delta
+                else:
+                    store(delta.key, delta)
     if updates is not None:
         rows = np.frombuffer(upd_rows, np.int64) if isinstance(upd_rows, bytes) else np.asarray(upd_rows, np.int64)
         updates.old_v, updates.new_v = old_v, new_v
         updates.old_leaf = old_leaf[rows]
         updates.new_leaf = new_leaf[rows]
         updates.deltas, updates.keys, updates.n_total = upd_deltas, upd_keys, n_total
+        updates.renamed = renamed
 
 
 def _pk_column(version, idx, present, n):
@@ -476,8 +567,11 @@ def _pk_column(version, idx, present, n):
     return out
 
 
-def dataset_diff(engine, base, target, ds_filter=None, reverse=False):
-    """RichBaseDataset.diff (kart/rich_base_dataset.py:170-181): {"meta": dict diff, "feature": DeltaDiff}"""
+def dataset_diff(engine, base, target, ds_filter=None, reverse=False, find_renames=False):
+    """RichBaseDataset.diff (kart/rich_base_dataset.py:170-181): {"meta": dict diff, "feature": DeltaDiff}
+
+    find_renames: re-keyed features fold into updates (diff_feature), when both versions exist and the
+    meta diff allows it (can_find_renames)"""
     S = structs()
     t = time.perf_counter()
     out = S.DatasetDiff()
@@ -490,13 +584,16 @@ def dataset_diff(engine, base, target, ds_filter=None, reverse=False):
         # child filter: ds_filter.get("feature", ds_filter.child_type()), :177)
         ffilter = ds_filter.get("feature", _NoKeys())
     batch = UpdateBatch()
+    kw = {}
+    if find_renames and old is not None and new is not None and can_find_renames(out["meta"]):
+        kw["find_renames"] = True
     with _gc_paused():
         if S.DeltaDiff is _deltas.DeltaDiff:  # this module's own DeltaDiff: its dict filled in place
             fd = S.DeltaDiff()
-            for _ in diff_feature(engine, base, target, ffilter, reverse=reverse, updates=batch, _collect=fd.data):
+            for _ in diff_feature(engine, base, target, ffilter, reverse=reverse, updates=batch, _collect=fd.data, **kw):
                 pass
         else:
-            fd = S.DeltaDiff(diff_feature(engine, base, target, ffilter, reverse=reverse, updates=batch))
+            fd = S.DeltaDiff(diff_feature(engine, base, target, ffilter, reverse=reverse, updates=batch, **kw))
     fd._kd_updates = batch
     out["feature"] = fd
     return out
@@ -529,9 +626,9 @@ class _NoKeys(frozenset):
     match_all = False
 
 
-def get_dataset_diff(engine, base, target, ds_filter=None):
+def get_dataset_diff(engine, base, target, ds_filter=None, find_renames=False):
     """diff_util.get_dataset_diff for one dataset present in either commit (kart/diff_util.py:51-95)"""
-    params = {}
+    params = {"find_renames": True} if find_renames else {}
     if base is None:
         base, target = target, base
         params["reverse"] = True
@@ -597,8 +694,9 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None):
         batch = _live_batch(feature_diff, old_version, new_version)
         if batch is not None:
             ups = batch.deltas
+            n_ren = _attach_pk_fields(batch.renamed, old_version, new_version)
             if not ups:
-                return 0
+                return n_ren
             if batch.prefetch is not None:  # read while the deltas were built (diff_feature)
                 fut, batch.prefetch = batch.prefetch, None
                 (od, oo), (nd, no) = fut.result()
@@ -606,8 +704,13 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None):
                 (od, oo), (nd, no) = _arena_pair(old_version, new_version, batch.old_leaf, batch.new_leaf)
         else:
             ups = [d for d in feature_diff.values() if d.type == "update"]
+            moved = [d for d in ups if d.old.key != d.new.key and _same_blob(d)]
+            if moved:
+                ids = set(map(id, moved))
+                ups = [d for d in ups if id(d) not in ids]
+            n_ren = _attach_pk_fields(moved, old_version, new_version)
             if not ups:
-                return 0
+                return n_ren
             od, oo = _blob_arena([d.old.value.args[0] for d in ups])
             nd, no = _blob_arena([d.new.value.args[0] for d in ups])
         t1 = time.perf_counter()
@@ -626,7 +729,29 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None):
                 d.changed_fields = nm if s == 0 else None
         if stats is not None:
             stats.update(read_s=t1 - t0, kernel_s=t2 - t1, attach_s=time.perf_counter() - t2)
-        return len(ups)
+        return len(ups) + n_ren
+
+
+def _same_blob(delta):
+    """both halves promise one blob (a re-keyed feature: find_renames folded its delete and insert)"""
+    try:
+        return delta.old.value.args[0].id == delta.new.value.args[0].id
+    except (AttributeError, IndexError):
+        return False
+
+
+def _attach_pk_fields(moved, old_version, new_version):
+    """changed_fields of re-keyed features whose blob is unchanged: the primary-key column name(s), in
+    _all_feature_keys order — every other value is byte for byte the same, so no kernel work"""
+    if not moved:
+        return 0
+    from .schema import union_keys
+
+    pk = {c.name for s in (old_version.schema, new_version.schema) if s is not None for c in s.pk_columns}
+    names = [k for k in union_keys(old_version.schema, new_version.schema) if k in pk]
+    for d in moved:
+        d.changed_fields = list(names)
+    return len(moved)
 
 
 def _arena_pair(old_v, new_v, old_leaf, new_leaf):
@@ -658,6 +783,8 @@ def _live_batch(feature_diff, old_version, new_version):
     if len(feature_diff) != batch.n_total:
         return None
     if not all(map(operator.is_, map(feature_diff.get, batch.keys), batch.deltas)):
+        return None
+    if batch.renamed and not all(feature_diff.get(d.key) is d for d in batch.renamed):
         return None
     return batch
 

@@ -244,6 +244,7 @@ class DiffPipeline:
         self._km = maps.kd_maps()
         self._perm_sides = None
         self._steps = {}  # kd_diff2_step argument blocks by form (_step_args)
+        self.ren = self.n_ren = None  # renames_step's pairs and their count (allocated on first use)
         # pk order of the deltas and updates (KD_KEY_INT): the passes sized by the pk range
         self.pk_order = bool(pk_order) and base.key_mode == N.KD_KEY_INT and gather is None
         if self.pk_order:
@@ -402,6 +403,35 @@ class DiffPipeline:
             st.d_upd_pk, st.d_upd_perm = self.u_pk.ptr, self.u_perm.ptr
         self._steps[form] = st
         return st
+
+    def renames_step(self, cap=None):
+        """queue kd_find_renames behind a step: the resident delta list and its device count, the sides
+        in the form the step joined (plain, or walk-order rows through the sort orders); the pairs and
+        their count stay in HBM (``ren``, ``n_ren``).  ``cap``: a bound of the delta count, which sizes
+        the grid and the pass's grow-only workspace (20 B per delta, and a table of 16 B times the power of
+        two at or above twice the deltas or the base entries, whichever are fewer).  Pass the tightest bound known — the count of an earlier
+        step, say; the default is the list's capacity, base.n + target.n + 1."""
+        if self.gather is not None:
+            raise ValueError("renames: a gathered shard holds only its own bucket range's OIDs")
+        cap = self.cap if cap is None else min(int(cap), self.cap)
+        if self.ren is None or self.ren.nbytes < 8 * (cap // 2 + 1):
+            self.ren = DevBuf(self.eng, 8 * (cap // 2 + 1))
+            self.n_ren = DevBuf(self.eng, 8)
+        if self.walk is not None and self.late:
+            st = self._step_args(True, self.pk_order and self.flags == 0)
+            sa, sb, oa, ob = st.base, st.target, st.base_order, st.target_order
+        else:
+            sa, sb, oa, ob = ctypes.pointer(self._sa), ctypes.pointer(self._sb), None, None
+        N.check(self.eng.L.kd_find_renames(self.eng.ctx, sa, sb, oa, ob, self.delta.ptr, cap, self.counts.ptr + 24,
+                                           N.KD_MEM_DEVICE, self.ren.ptr, self.n_ren.ptr, N.KD_MEM_DEVICE),
+                "kd_find_renames")
+
+    def renames(self, cap=None):
+        """after ``step()``: uint32 [k, 2] (delta index of a delete, delta index of the insert with the
+        same blob OID), ascending by the delete — host copy (synchronous)"""
+        self.renames_step(cap)
+        k = int(self.n_ren.download(np.uint64, 1)[0])
+        return self.ren.download(np.uint32, 2 * k).reshape(k, 2)
 
     def results(self):
         """host copies (synchronous): counts dict, delta [n,2], upd [m,2], masks, status"""

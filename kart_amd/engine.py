@@ -237,6 +237,33 @@ class Engine:
                                          min(lo), max(hi), d_pk.ptr, d_perm.ptr), "kd_delta_pk_order")
         return d_pk.download(np.int64, n), d_perm.download(np.uint32, n)
 
+    def find_renames(self, base, target, delta):
+        """delta uint32 [n, 2] (the (base | NONE, target | NONE) records of a two-way diff of the two
+        PackedSides, in its order) -> uint32 [k, 2]: (delta index of a delete, delta index of the insert
+        with the same blob OID), ascending by the delete (kd_find_renames: at most one pair per OID, the
+        last delete with the last insert, as WorkingCopy.find_renames pairs them)"""
+        delta = np.ascontiguousarray(delta, np.uint32).reshape(-1, 2)
+        n = int(delta.shape[0])
+        if n < 2:
+            return np.zeros((0, 2), np.uint32)
+        if base.walk_rows or target.walk_rows:  # OIDs in walk order: read through the sort orders
+            from .device import DevBuf, perm_dev
+
+            (sa, oa, ka), (sb, ob, kb) = perm_dev(self, base), perm_dev(self, target)
+            d_delta = DevBuf.from_numpy(self, delta.reshape(-1))
+            d_ren, d_n = DevBuf(self, 8 * (n // 2 + 1)), DevBuf(self, 8)
+            N.check(self.L.kd_find_renames(self.ctx, ctypes.byref(sa), ctypes.byref(sb), oa.ptr, ob.ptr, d_delta.ptr, n,
+                                           None, N.KD_MEM_DEVICE, d_ren.ptr, d_n.ptr, N.KD_MEM_DEVICE), "kd_find_renames")
+            k = int(d_n.download(np.uint64, 1)[0])
+            del ka, kb
+            return d_ren.download(np.uint32, 2 * k).reshape(k, 2)
+        sa, sb = base.kd_side(), target.kd_side()
+        ren = np.zeros((n // 2 + 1, 2), np.uint32)
+        k = ctypes.c_uint64()
+        N.check(self.L.kd_find_renames(self.ctx, ctypes.byref(sa), ctypes.byref(sb), None, None, N.ptr(delta), n, None,
+                                       N.KD_MEM_HOST, N.ptr(ren), ctypes.byref(k), N.KD_MEM_HOST), "kd_find_renames")
+        return ren[:int(k.value)].copy()
+
     def fielddiff(self, old_data, old_off, new_data, new_off, pairs, maps, size_hint=0):
         """Blob arenas (uint8 data, uint64 off[n+1]) per side; pairs uint32 [n, 2] (old blob,
         new blob) or None (blob u on both sides); maps: schema.FieldMaps; size_hint: the typical

@@ -346,6 +346,32 @@ def polygons_layer(n, seed=SEED, shard=None, batch=1 << 20, delta_blobs=False, s
                  int(np.count_nonzero(plan == 3)))
 
 
+def renumber_pks(layer, share, seed=SEED):
+    """Bench-only (scripts/renames_bench.py): a re-import that renumbers primary keys.  ``share`` of the
+    target entries the diff leaves alone (same key and OID on both sides) move to fresh pks above every
+    pk of either side, their OIDs and blobs untouched — each shows as one delete plus one insert of one
+    OID.  Returns (layer with the new target in key order, number of re-keyed features)."""
+    B, T = layer.base, layer.target
+    pos = np.minimum(np.searchsorted(B.key, T.key), max(B.n - 1, 0))
+    same = (B.key[pos] == T.key) & (B.oid[pos] == T.oid).all(1) if B.n else np.zeros(T.n, bool)
+    cand = np.nonzero(same)[0]
+    pick = np.sort(np.random.default_rng(seed).choice(cand, int(share * cand.size), replace=False))
+    top = max(int(packing.int_keys_to_pks(s.key).max()) for s in (B, T) if s.n)
+    key = T.key.copy()
+    key[pick] = walkkey.int_keys(np.arange(top + 1, top + 1 + pick.size, dtype=np.int64))
+    order = np.argsort(key, kind="stable")
+    target = packing.PackedSide(key=key[order], oid=np.ascontiguousarray(T.oid[order]), key_mode=0,
+                                order=np.arange(T.n, dtype=np.int64), encoding=T.encoding)
+    data, off = layer.target_blobs
+    lens = (off[1:] - off[:-1])[order]
+    noff = np.zeros(T.n + 1, np.uint64)
+    np.cumsum(lens, out=noff[1:])
+    src = np.repeat(off[:-1][order].astype(np.int64) - noff[:-1].astype(np.int64), lens.astype(np.int64))
+    ndata = np.ascontiguousarray(data[src + np.arange(int(noff[-1]), dtype=np.int64)])
+    return Layer(B, target, layer.base_blobs, (ndata, noff), layer.schema, layer.legends, layer.n_insert + pick.size,
+                 layer.n_update, layer.n_delete + pick.size), int(pick.size)
+
+
 def shard_rank_range(rank, world, n_pks):
     """[lo, hi) of rank's bucket-range shard of a layer with int pks 0..n_pks-1, in rank-mapped bucket
     space (the key's top 24 bits): a contiguous run of the tree walk holding about n_pks / world pks
