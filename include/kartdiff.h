@@ -15,6 +15,8 @@
  *                     paired on the GPU, at any size (the reference caps its pass at 400 deltas, :688).
  *   kd_merge3      <- repo.merge_trees(ancestor, ours, theirs) (kart/merge.py:99-100; libgit2
  *                     git_merge_trees) feeding MergeIndex.from_pygit2_index (kart/merge_util.py:92-103).
+ *   kd_tree_hash   <- index.write_tree(repo) (kart/merge.py:122; libgit2 git_index_write_tree): the ids
+ *                     and bodies of one level of git tree objects, SHA-1 on the GPU.
  *   kd_envelopes   <- SpatialFilter.matches envelope quick-check (kart/spatial_filter/__init__.py:534-590,
  *                     709-734) + get_envelope_for_indexing/EnvelopeEncoder.encode for an identity
  *                     CRS (kart/spatial_filter/index.py:485-579,639-707).
@@ -261,6 +263,57 @@ int kd_find_renames(kd_ctx* ctx, const kd_side* base, const kd_side* target,
                     const uint32_t* base_order, const uint32_t* target_order,
                     const uint32_t* delta, uint64_t n_delta, const uint64_t* d_n_delta, uint32_t list_mem,
                     uint32_t* ren, uint64_t* n_ren, uint32_t out_mem);
+
+/* -------- git tree objects: ids and bodies of one level of trees -------- */
+/* <- index.write_tree(repo) (kart/merge.py:122).  Tree t consists of entries seg[t] .. seg[t+1] of e.
+ * Its body is the concatenation of "<mode> <name>\0<20 oid bytes>" over them, mode "100644" for
+ * KD_TE_BLOB and "40000" for KD_TE_TREE (one kind per call); its id is
+ * SHA1("tree " + decimal(len(body)) + "\0" + body).  An empty run gives git's empty tree,
+ * 4b825dc642cb6eb9a060e54bf8d69288fbee4904.  A pure function of the inputs, bitwise reproducible.
+ *
+ * status[t]: 0 ok; 1 the run is not strictly ascending in git's order (without KD_TH_RANK_NAMES);
+ * 2 two entries of the run share a name (with it); 3 a name is empty, longer than 255 bytes, or holds
+ * '/' or NUL.  Where several apply the largest is reported.  Where status is non-zero the id is 20
+ * zero bytes, the body is empty and body_off[t+1] == body_off[t].
+ * Git's order: names compare as unsigned bytes; a blob's name as if it ended in NUL (a prefix comes
+ * first: a, a-, a0, ab), a tree's as if it ended in '/' (a-, a, a0, ab).  The rule of e->kind is used.
+ * KD_TH_RANK_NAMES (KD_TE_BLOB only, else KD_EINVAL): the entries of a run arrive in any order and are
+ * ordered by the blob rule before formatting (a KD_KEY_HASH side in key order is grouped by leaf tree
+ * but not in filename order inside one); runs of up to 512 entries, a longer one: KD_EUNSUPPORTED.
+ * Without the flag a run may have any length.
+ *
+ * name_off[n+1] are byte offsets into name, ascending; oid and tree_oid are 4-byte aligned, and
+ * tree_oid has the layout of kd_tree_entries.oid, so a device-resident level is the next level's
+ * oid array as it stands.  seg lives where e's arrays live (e->mem); out_mem says where tree_oid,
+ * status, body and body_off live.  body / body_off (both or neither): the object payloads without
+ * the "tree <len>\0" header, tree t's at body[body_off[t] .. body_off[t+1]]; KD_EINVAL when body_cap is
+ * below body_off[n_trees].  Host arrays are staged by the library and the call returns with the
+ * results.  With device outputs the hashing is queued on the context's stream and the call returns
+ * without waiting for it; every call waits once, after the sizing kernels, for 32 bytes (the arena's
+ * size, the body bytes, the long-run flag) that size the arena and decide the two errors above.
+ * Host seg and name_off are checked (KD_EINVAL if they descend or run past n); device ones are
+ * clamped to the entries and the name bytes there are.
+ * Workspace (grow-only, kept by the context): 4 bytes per entry (8 with KD_TH_RANK_NAMES), 44 bytes
+ * per tree, and an arena of every object padded to SHA-1's 64-byte blocks: the body bytes plus
+ * between 16 and 98 bytes per tree; host arrays add their device copies.
+ * KD_EINVAL: NULL where a pointer is required, an unknown kind or flag, body without body_off,
+ * n or n_trees above 2^32 - 2. */
+#define KD_TE_BLOB 0u        /* every entry is "100644 <name>\0<oid>" */
+#define KD_TE_TREE 1u        /* every entry is "40000 <name>\0<oid>"  */
+#define KD_TH_RANK_NAMES 1u  /* entries of a run may arrive in any order (KD_TE_BLOB only) */
+
+typedef struct kd_tree_entries {
+    uint64_t n;
+    const uint8_t* name;
+    const uint64_t* name_off; /* [n+1] */
+    const uint8_t* oid;       /* [n*20], 4-byte aligned */
+    uint32_t kind;            /* KD_TE_BLOB | KD_TE_TREE, one kind per call */
+    uint32_t mem;             /* KD_MEM_HOST | KD_MEM_DEVICE */
+} kd_tree_entries;
+
+int kd_tree_hash(kd_ctx* ctx, const kd_tree_entries* e, const uint64_t* seg, uint64_t n_trees, uint32_t flags,
+                 uint8_t* tree_oid, uint8_t* status, uint8_t* body, uint64_t* body_off, uint64_t body_cap,
+                 uint32_t out_mem);
 
 /* -------- three-way merge classification -------- */
 int kd_merge3(kd_ctx* ctx, const kd_side* ancestor, const kd_side* ours, const kd_side* theirs,

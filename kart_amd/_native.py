@@ -19,6 +19,9 @@ KD_WALK_ALL = -1
 KD_NONE = 0xFFFFFFFF
 KD_MEM_HOST = 0
 KD_MEM_DEVICE = 1
+KD_TE_BLOB = 0
+KD_TE_TREE = 1
+KD_TH_RANK_NAMES = 1
 KD_KEY_INT = 0
 KD_KEY_HASH = 1
 KD_DIFF_UNORDERED = 0x1
@@ -79,6 +82,18 @@ class KdSide(ctypes.Structure):
         ("name_off", ctypes.c_void_p),
         ("mem", ctypes.c_uint32),
         ("key_mode", ctypes.c_uint32),
+    ]
+
+
+class KdTreeEntries(ctypes.Structure):
+    """kd_tree_entries (kd_tree_hash): the (name, oid) entries of one level of git trees"""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("name", ctypes.c_void_p),
+        ("name_off", ctypes.c_void_p),
+        ("oid", ctypes.c_void_p),
+        ("kind", ctypes.c_uint32),
+        ("mem", ctypes.c_uint32),
     ]
 
 
@@ -224,6 +239,11 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.POINTER(KdSide), ctypes.POINTER(KdSide), ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_uint32],
+    ),
+    "kd_tree_hash": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(KdTreeEntries), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32],
     ),
     "kd_merge3": (
         ctypes.c_int,

@@ -264,6 +264,57 @@ class Engine:
                                        N.KD_MEM_HOST, N.ptr(ren), ctypes.byref(k), N.KD_MEM_HOST), "kd_find_renames")
         return ren[:int(k.value)].copy()
 
+    def tree_hash(self, names, name_off, oids, seg, kind, rank=False, bodies=False, body_cap=None):
+        """The ids of one level of git trees (kd_tree_hash).  Tree t consists of entries
+        seg[t] .. seg[t+1]: names uint8 arena with name_off uint64 [n+1], oids uint8 [n, 20], all of
+        one ``kind`` (KD_TE_BLOB / KD_TE_TREE); ``rank``: the entries of a run come in any order
+        (blobs, runs of up to 512).  Returns (ids uint8 [n_trees, 20], status uint8 [n_trees]) plus
+        (body uint8, body_off uint64 [n_trees+1]) with ``bodies`` (``body_cap``: the room for them in
+        bytes, by default what the entries can need).  numpy arrays in: numpy arrays
+        out.  If any input is a DevBuf the others are uploaded, the call is the device form and the
+        results are DevBufs (the ids are the next level's ``oids`` as they stand)."""
+        from .device import DevBuf
+
+        ins = [names, name_off, oids, seg]
+        flags = N.KD_TH_RANK_NAMES if rank else 0
+        e = N.KdTreeEntries()
+        e.kind = int(kind)
+        if any(isinstance(x, DevBuf) for x in ins):
+            dts = (np.uint8, np.uint64, np.uint8, np.uint64)
+            d = [x if isinstance(x, DevBuf) else DevBuf.from_numpy(self, np.ascontiguousarray(x, dt).reshape(-1))
+                 for x, dt in zip(ins, dts)]
+            n, nt = d[2].nbytes // 20, d[3].nbytes // 8 - 1
+            if d[1].nbytes != 8 * (n + 1) or nt < 0:
+                raise ValueError("tree_hash: name_off must hold n + 1 offsets, seg n_trees + 1")
+            e.n, e.name, e.name_off, e.oid, e.mem = n, d[0].ptr, d[1].ptr, d[2].ptr, N.KD_MEM_DEVICE
+            ids, status = DevBuf(self, 20 * nt), DevBuf(self, nt)
+            cap = 28 * n + d[0].nbytes if body_cap is None else int(body_cap)
+            body, body_off = (DevBuf(self, cap), DevBuf(self, 8 * (nt + 1))) if bodies else (None, None)
+            N.check(self.L.kd_tree_hash(self.ctx, ctypes.byref(e), d[3].ptr, nt, flags, ids.ptr, status.ptr,
+                                        body.ptr if bodies else None, body_off.ptr if bodies else None, cap,
+                                        N.KD_MEM_DEVICE), "kd_tree_hash")
+            if any(x is not y for x, y in zip(ins, d)):
+                self.sync()  # (the uploaded copies are freed on return)
+            return (ids, status, body, body_off) if bodies else (ids, status)
+        names = np.ascontiguousarray(names, np.uint8).reshape(-1)
+        name_off = np.ascontiguousarray(name_off, np.uint64)
+        oids = np.ascontiguousarray(oids, np.uint8).reshape(-1, 20)
+        seg = np.ascontiguousarray(seg, np.uint64)
+        n, nt = int(oids.shape[0]), int(seg.shape[0]) - 1
+        if name_off.shape[0] != n + 1 or nt < 0:
+            raise ValueError("tree_hash: name_off must hold n + 1 offsets, seg n_trees + 1")
+        e.n, e.name, e.name_off, e.mem = n, N.ptr(names) if names.size else N.ptr(_PAD), N.ptr(name_off), N.KD_MEM_HOST
+        e.oid = N.ptr(oids) if n else N.ptr(_PAD)
+        ids, status = np.zeros((max(nt, 1), 20), np.uint8), np.zeros(max(nt, 1), np.uint8)
+        cap = 28 * n + int(names.size) if body_cap is None else int(body_cap)
+        body = np.zeros(max(cap, 1), np.uint8) if bodies else None
+        body_off = np.zeros(nt + 1, np.uint64) if bodies else None
+        N.check(self.L.kd_tree_hash(self.ctx, ctypes.byref(e), N.ptr(seg), nt, flags, N.ptr(ids), N.ptr(status),
+                                    N.ptr(body), N.ptr(body_off), cap, N.KD_MEM_HOST), "kd_tree_hash")
+        if bodies:
+            return ids[:nt], status[:nt], body[:int(body_off[nt])], body_off
+        return ids[:nt], status[:nt]
+
     def fielddiff(self, old_data, old_off, new_data, new_off, pairs, maps, size_hint=0):
         """Blob arenas (uint8 data, uint64 off[n+1]) per side; pairs uint32 [n, 2] (old blob,
         new blob) or None (blob u on both sides); maps: schema.FieldMaps; size_hint: the typical

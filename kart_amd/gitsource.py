@@ -201,6 +201,15 @@ class GitRepo:
                            capture_output=True)
             return subprocess.run(["git", "write-tree"], env=env, check=True, capture_output=True).stdout.decode().strip()
 
+    def write_objects(self, pack):
+        """the objects of a pack stream (treebuild.pack_objects) into the object store: one
+        ``git unpack-objects``, which keeps each as a loose object and drops those the repository
+        already has; then the native reader looks at the store again"""
+        if int.from_bytes(pack[8:12], "big") == 0:
+            return
+        subprocess.run(["git", "unpack-objects", "-q"], input=pack, env=self.env, check=True, capture_output=True)
+        self.odb.refresh()
+
     # ---- dataset versions -----------------------------------------------------------------------
     def tree_at(self, spec, path):
         """the OID of the tree at ``path`` in revision ``spec``, or None"""

@@ -63,6 +63,7 @@ class _LazyEntries(dict):
     def __init__(self, build):
         super().__init__()
         self._build = build
+        self.edited = False  # a caller set or deleted an entry (write_tree's engine path reads the merge result)
 
     def _fill(self):
         if self._build is not None:
@@ -108,10 +109,12 @@ class _LazyEntries(dict):
 
     def __setitem__(self, k, v):
         self._fill()
+        self.edited = True
         dict.__setitem__(self, k, v)
 
     def __delitem__(self, k):
         self._fill()
+        self.edited = True
         dict.__delitem__(self, k)
 
 
@@ -125,6 +128,11 @@ class MergeIndex:
         self.conflicts = conflicts
         self.resolves = dict(resolves or {})
         self.automerge_candidates = []  # conflict keys libgit2 might text-merge (NUL-free blobs)
+        # what write_tree's engine path reads: merge_trees keeps its classification here (_FeaturePart),
+        # merge_repo the non-feature entries and its datasets' indexes
+        self.feature_part = None
+        self.files = None
+        self.parts = None
 
     def __iter__(self):
         return iter(self.entries.values())
@@ -145,11 +153,17 @@ class MergeIndex:
             raise TypeError("resolve key must be str", type(key))
         self.resolves[key] = list(resolve)
 
-    def write_tree(self, repo):
+    def write_tree(self, repo, engine=None):
         """index.write_tree(repo) (kart/merge.py:122): the merged tree's id; like libgit2, refuses an
-        index with unresolved conflicts.  ``repo``: kart_amd.gitsource.GitRepo."""
+        index with unresolved conflicts.  ``repo``: kart_amd.gitsource.GitRepo.
+
+        With ``engine`` (an index from merge_trees / merge_repo): the same id, the feature trees
+        hashed on the GPU from the merge's arrays (treebuild.feature_tree; no Entry per leaf), the few
+        trees above them on the host, every new tree object written through one pack."""
         if self.unresolved_conflicts:
             raise ValueError("cannot write a tree from an index with unresolved conflicts")
+        if engine is not None:
+            return _write_tree_engine(self, repo, engine)
         lines = b"".join(b"%o %s\t%s\0" % (e.mode, e.id.encode(), e.path.encode()) for e in self.entries.values())
         return repo.write_index_tree(lines)
 
@@ -161,14 +175,19 @@ def _side(version, encoding, engine=None):
     return version.pack(engine)
 
 
-def merge_trees(engine, ancestor, ours, theirs, prefix="", ours_all=None):
+class _FeaturePart(namedtuple("_FeaturePart", ("vers", "sides", "r", "prefix", "encoding", "ours_all", "ours_leaves"))):
+    """one dataset's classification as merge_trees leaves it on its MergeIndex"""
+
+
+def merge_trees(engine, ancestor, ours, theirs, prefix="", ours_all=None, ours_leaves=None):
     """Three-way classification of one dataset's feature tree (DatasetVersion or None for each of
     ancestor / ours / theirs) -> MergeIndex of its feature paths (``prefix`` + relative path, e.g.
     "<ds>/.table-dataset/feature/").  Entries and conflicts follow libgit2's rule exactly.
 
     Versions from a pruned walk (``.partial``: only the subtrees where ours and theirs differ,
     gitsource.merge_versions) classify the same; ``ours_all() -> [(rel path, oid hex)]`` then lists
-    every leaf of ours, for the merged entries outside those subtrees (ours == theirs there)."""
+    every leaf of ours, for the merged entries outside those subtrees (ours == theirs there);
+    ``ours_leaves() -> odb.Leaves`` gives the same leaves as arrays (write_tree's engine path)."""
     present = next((v for v in (ours, theirs, ancestor) if v is not None), None)
     if present is None:
         return MergeIndex({}, {})
@@ -213,6 +232,7 @@ def merge_trees(engine, ancestor, ours, theirs, prefix="", ours_all=None):
 
     mi = MergeIndex(_LazyEntries(build), conflicts)
     mi.n_clean = r.n_clean
+    mi.feature_part = _FeaturePart(vers, sides, r, prefix, present.encoding, ours_all, ours_leaves)
     mi.automerge_candidates = [str(k) for k, j in enumerate(order) if mm[j]]
     return mi
 
@@ -264,11 +284,14 @@ def merge_repo(engine, repo, ancestor, ours, theirs):
         pre = f"{ds}/.table-dataset/feature/"
         vers = repo.merge_versions(*specs, ds)  # pruned to the subtrees where ours and theirs differ
 
-        def ours_all(pre=pre):
+        def ours_leaves(pre=pre):
             (lv,) = repo.walk([ours], pre.rstrip("/"))
-            return lv.items()
+            return lv
 
-        parts.append(merge_trees(engine, *vers, prefix=pre, ours_all=ours_all))
+        def ours_all(ours_leaves=ours_leaves):
+            return ours_leaves().items()
+
+        parts.append(merge_trees(engine, *vers, prefix=pre, ours_all=ours_all, ours_leaves=ours_leaves))
     for mi in parts:
         conf.extend(mi.conflicts.values())
     conf.sort(key=lambda c: next(e for e in c if e).path.encode())
@@ -280,9 +303,108 @@ def merge_repo(engine, repo, ancestor, ours, theirs):
             yield from mi.entries.values()
 
     out = MergeIndex(_LazyEntries(build), conflicts)
+    out.files, out.parts = entries, parts
     keys = {id(c): k for k, c in conflicts.items()}
     out.automerge_candidates = [keys[id(mi.conflicts[k])] for mi in parts for k in mi.automerge_candidates]
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# write_tree(repo, engine): the merged feature leaves as arrays, their trees on the GPU
+def _fixed(arena, off):
+    """the strings of (arena, off) as one numpy bytes array (zero-padded to the longest)"""
+    off = np.asarray(off).astype(np.int64)
+    n = off.shape[0] - 1
+    lens = off[1:] - off[:-1]
+    w = max(int(lens.max()) if n else 1, 1)
+    m = np.zeros((n, w), np.uint8)
+    m[np.repeat(np.arange(n), lens), np.arange(int(lens.sum())) - np.repeat(off[:-1] - off[0], lens)] = \
+        np.asarray(arena, np.uint8)[int(off[0]):int(off[-1])] if n else 0
+    return m.view(f"S{w}").reshape(-1)
+
+
+def _merged_leaves(mi):
+    """(rel path arena, offsets, oids [n, 20]) of one dataset's merged feature leaves — the set
+    merge_trees' entries hold: ours' kept rows, the rows taken from theirs, every conflicted path's
+    last stage, and ours' leaves outside a pruned walk's opened subtrees — in no particular order"""
+    from . import treebuild as TB
+
+    fp = mi.feature_part
+    _, o, t = fp.vers
+    so, st = fp.sides[1], fp.sides[2]
+    md, cf = fp.r.mdelta, fp.r.conflict
+    pieces = []
+    if o is not None and getattr(o, "partial", False):
+        if fp.ours_leaves is not None:
+            lv = fp.ours_leaves()
+            lp, lo, lid = lv.paths, lv.off, lv.oids
+        elif fp.ours_all is not None:
+            items = fp.ours_all()
+            lp, lo = TB.pack_strings([p.encode() for p, _ in items])
+            lid = np.frombuffer(b"".join(bytes.fromhex(x) for _, x in items), np.uint8)
+        else:
+            raise ValueError("write_tree: a pruned merge needs ours' full leaf list")
+        lid = np.asarray(lid, np.uint8).reshape(-1, 20)
+        if lid.shape[0]:
+            outside = np.nonzero(~np.isin(_fixed(lp, lo), _fixed(o.rel_paths, o.rel_off)))[0]
+            pieces.append(TB.gather_rows(lp, lo, outside) + (lid[outside],))
+    if o is not None and o.n:
+        skip = np.zeros(so.n, bool)
+        if md.size:
+            skip[md[:, 0][md[:, 0] != N.KD_NONE].astype(np.int64)] = True
+        if cf.size:
+            skip[cf[:, 1][cf[:, 1] != N.KD_NONE].astype(np.int64)] = True
+        rows = np.asarray(so.order).astype(np.int64)[np.nonzero(~skip)[0]]
+        pieces.append(TB.gather_rows(o.rel_paths, o.rel_off, rows) + (o.oids[rows],))
+    if md.size:
+        rows = np.asarray(st.order).astype(np.int64)[md[:, 1][md[:, 1] != N.KD_NONE].astype(np.int64)]
+        if rows.size:
+            pieces.append(TB.gather_rows(t.rel_paths, t.rel_off, rows) + (t.oids[rows],))
+    last = [c.theirs or c.ours or c.ancestor for c in mi.conflicts.values()]
+    if last:
+        a, off = TB.pack_strings([e.path[len(fp.prefix):].encode() for e in last])
+        pieces.append((a, off, np.frombuffer(b"".join(bytes.fromhex(e.id) for e in last), np.uint8).reshape(-1, 20)))
+    if not pieces:
+        return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros((0, 20), np.uint8)
+    arena = np.concatenate([p[0] for p in pieces])
+    lens = np.concatenate([np.diff(p[1].astype(np.int64)) for p in pieces])
+    off = np.zeros(lens.size + 1, np.uint64)
+    off[1:] = np.cumsum(lens)
+    return arena, off, np.concatenate([p[2] for p in pieces])
+
+
+def _write_tree_engine(mi, repo, engine):
+    from . import treebuild as TB
+
+    if mi.parts is not None:
+        files, parts = mi.files, mi.parts
+    elif mi.feature_part is not None:
+        files, parts = {}, [mi]
+    else:
+        raise ValueError("write_tree(repo, engine) needs an index from merge_trees or merge_repo")
+    parts = [x for x in parts if x.feature_part is not None]  # (a dataset absent from all three sides has none)
+    if any(getattr(x.entries, "edited", False) for x in [mi, *parts]):
+        raise ValueError("write_tree(repo, engine): the entries were edited; write_tree(repo) writes those")
+    subtrees, objects = {}, []
+    for part in parts:
+        arena, off, oids = _merged_leaves(part)
+        enc = part.feature_part.encoding
+        # the pieces into directory order (a stable sort of the directory prefix); inside a directory
+        # the kernel ranks the names (a leaf tree holds 64 entries, or a handful under hash keys)
+        arena, off, oids = TB.group_by_directory(arena, off, oids, enc)
+        ft = TB.feature_tree(engine, arena, off, oids, enc, rank=True, bodies=True)
+        if ft is None:
+            continue
+        subtrees[part.feature_part.prefix.rstrip("/")] = ft.root
+        objects.extend(ft.objects)
+    root, built = TB.host_trees({p: (e.mode, e.id) for p, e in files.items()}, subtrees)
+    if built:
+        boff = np.zeros(len(built) + 1, np.uint64)
+        boff[1:] = np.cumsum([len(b) for _, b in built])
+        objects.append((np.frombuffer(b"".join(i for i, _ in built), np.uint8).reshape(-1, 20),
+                        np.frombuffer(b"".join(b for _, b in built), np.uint8), boff))
+    repo.write_objects(TB.pack_objects(*TB.concat_objects(objects)))
+    return root.hex()
 
 
 # ---------------------------------------------------------------------------------------------
