@@ -704,6 +704,56 @@ int kd_odb_read(kd_odb* odb, const uint8_t oid[20], int* type, uint8_t** data, u
  * status[i] 0 ok, 1 missing (empty), 2 corrupt / not a blob (empty).  threads 0 = up to 16. */
 int kd_odb_read_batch(kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, uint8_t** data,
                       uint64_t* off, uint8_t* status);
+
+/* -------- device inflate: zlib streams decoded on the GPU (opt-in route of the batched read) -------- */
+/* Kart imports with `git fast-import --depth=0` (kart/fast_import.py:204,273): a feature blob of an
+ * imported layer is a plain deflate stream in the pack, its inflated size in the entry header.  The
+ * decoder (kart_amd/csrc/kd_inflate.h, written from RFC 1950 / RFC 1951) handles the zlib header
+ * (CM = 8, window <= 32 KiB, FCHECK, no FDICT), stored / fixed / dynamic blocks and the Adler-32
+ * trailer.  Status of one stream: */
+#define KD_INF_OK 0u
+#define KD_INF_EHEADER 1u  /* bad zlib header                                                        */
+#define KD_INF_EBTYPE 2u   /* reserved block type                                                    */
+#define KD_INF_ESTORED 3u  /* stored LEN / NLEN mismatch                                             */
+#define KD_INF_ELENS 4u    /* bad code lengths: over-subscribed; incomplete (other than one code of one
+                              bit, or an empty distance set); a repeat with no previous length or running
+                              past HLIT + HDIST; no end-of-block code; HLIT > 286 or HDIST > 30      */
+#define KD_INF_ESYMBOL 5u  /* literal/length 286 / 287, distance 30 / 31, or a code the set leaves out */
+#define KD_INF_EDIST 6u    /* a distance reaching before the stream's own output                     */
+#define KD_INF_EOVER 7u    /* more output than the expected size                                     */
+#define KD_INF_ESHORT 8u   /* end of stream before the expected size                                 */
+#define KD_INF_ESRC 9u     /* source exhausted: a bit needed at or beyond the stream's bound         */
+#define KD_INF_EADLER 10u  /* Adler-32 mismatch                                                      */
+#define KD_INF_ERANGE 11u  /* device offsets only: an item's offsets descend or pass off[n]          */
+#define KD_INF_MAX (256u << 10) /* the largest blob kd_odb_read_batch_device inflates on the device  */
+/* Item i: src[src_off[i] .. src_off[i+1]) -> dst[dst_off[i] .. dst_off[i+1]), status[i] = KD_INF_*.
+ * kind[i] (NULL: all 0): 0 a zlib stream whose inflated size is its dst range exactly — the src range
+ * only bounds the stream, bytes after its end are ignored; 1 raw bytes copied as they are (the ranges'
+ * sizes must agree: KD_INF_ESRC / KD_INF_EOVER).  A failing item stops at its first error: the bytes of
+ * its own dst range are unspecified, nothing outside that range is written.  One launch of
+ * k_inf_streams, one lane per item.
+ * mem = KD_MEM_HOST: every array is host memory, staged by the library (workspace: the context's
+ * grow-only slots), offsets are checked (descending: KD_EINVAL) and the call returns with the results.
+ * mem = KD_MEM_DEVICE: every array is device memory, src readable up to src_off[n] + 8 bytes, and the
+ * call is queued on the context's stream. */
+int kd_inflate_batch(kd_ctx* ctx, const uint8_t* src, const uint64_t* src_off, const uint8_t* kind, uint64_t n,
+                     uint8_t* dst, const uint64_t* dst_off, uint8_t* status, uint32_t mem);
+/* kd_odb_read_batch with the arena in HBM: out->data / out->off (kd_malloc'd, mem = KD_MEM_DEVICE, the
+ * caller kd_mfree's both) hold what kd_odb_read_batch returns in *data / off, status (host, [n]) its
+ * codes, for every input.  A packed, non-delta blob of at most KD_INF_MAX bytes is shipped compressed
+ * (the span from its data to size + size/4096 + size/16384 + size/2^25 + 13 bytes on, clipped to the
+ * pack's trailer) and inflated by kd_inflate_batch; every other object (deltas, loose objects, larger
+ * blobs, ids no pack holds) is read on the host as before and uploaded as a raw item of the same
+ * launch.  A device item that fails is read again on the host, so the result does not rest on that
+ * bound.  stats: streams inflated on the device, objects read on the host, compressed bytes uploaded,
+ * device items that needed the host read.  Returns after the results are complete.
+ * Costs to know: the sources of one call are gathered into one pinned (page-locked) host buffer the
+ * store keeps and only grows until kd_odb_close — the largest call's compressed spans plus host-read
+ * bytes, plus a quarter (about 1.3 GB after a read of 4M blobs of 240 B).  A raw item is copied by one
+ * lane, a byte at a time, whatever its size: a host-class blob of many megabytes holds its wave for as
+ * long as that takes. */
+int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, kd_blobs* out,
+                             uint8_t* status, uint64_t stats[4]);
 /* A walk's leaves for one root, one block (kd_free): leaf i = path[path_off[i] .. path_off[i+1])
  * relative to the walked tree, '/'-separated, in git path order (what `git ls-tree -r` lists). */
 typedef struct kd_leaves {

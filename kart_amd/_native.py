@@ -35,6 +35,10 @@ KD_GH_GEOM, KD_GH_NULL, KD_GH_FALLBACK = 0, 2, 3
 KD_GF_RECT = 0x1
 KD_GF_DELTA_HEADS = 0x2  # the geometry heads are in delta order (slot d = delta d)
 KD_GF_EXACT = 0x4  # kd_geom_refine: decide what FP64 cannot certify in exact arithmetic
+# kd_inflate_batch's status of one stream (kartdiff.h KD_INF_*)
+(KD_INF_OK, KD_INF_EHEADER, KD_INF_EBTYPE, KD_INF_ESTORED, KD_INF_ELENS, KD_INF_ESYMBOL, KD_INF_EDIST, KD_INF_EOVER,
+ KD_INF_ESHORT, KD_INF_ESRC, KD_INF_EADLER, KD_INF_ERANGE) = range(12)
+KD_INF_MAX = 256 << 10  # the largest blob kd_odb_read_batch_device inflates on the device
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -384,6 +388,16 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(c_u8p), ctypes.c_void_p,
          ctypes.c_void_p],
+    ),
+    "kd_inflate_batch": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32],
+    ),
+    "kd_odb_read_batch_device": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(KdBlobs),
+         ctypes.c_void_p, c_u64p],
     ),
     "kd_walk": (
         ctypes.c_int,

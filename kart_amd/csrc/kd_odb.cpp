@@ -146,6 +146,10 @@ struct kd_odb {
     std::vector<Reader*> pool;
     // options (kd_odb_set_option; kd_odb_open seeds them from the environment)
     int zlib_only = 0;  // "zlib" [KD_ODB_ZLIB]: 1 = inflate with zlib even when libdeflate is present (A/B)
+    // kd_odb_read_batch_device: the pinned staging its sources are gathered into (grow-only), one call at a time
+    std::mutex dev_mu;
+    u8* pin = nullptr;
+    u64 pin_cap = 0;
 };
 
 namespace {
@@ -849,8 +853,10 @@ extern "C" int kd_odb_get_option(kd_odb* odb, const char* name, int64_t* value) 
 }
 
 extern "C" int kd_odb_close(kd_odb* odb) {
-    if (odb)
+    if (odb) {
         for (Reader* r : odb->pool) delete r;
+        if (odb->pin) kd_host_free(odb->pin);
+    }
     delete odb;
     return KD_OK;
 }
@@ -951,6 +957,189 @@ extern "C" int kd_odb_read_batch(kd_odb* odb, const uint8_t* oids, uint64_t n, i
             if (off[i + 1] > off[i]) memcpy(p + off[i], part[chunk_of[i]].data() + at[i], off[i + 1] - off[i]);
     });
     *data = p;
+    return KD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the batched read with the arena in HBM (kd_inflate.hip inflates the plain packed blobs)
+// ---------------------------------------------------------------------------------------------
+namespace kd {
+// kd_inflate.hip: upload the gathered sources, one launch of k_inf_streams, the status bytes back
+int inflate_from_host(kd_ctx* ctx, const uint8_t* h_src, const uint64_t* h_src_off, const uint8_t* h_kind, uint64_t n,
+                      uint8_t* d_dst, const uint64_t* h_dst_off, uint64_t* d_dst_off, uint8_t* h_status);
+}
+
+namespace {
+// the most a deflate stream of `size` bytes is taken to occupy (a stored block's 5 bytes per 16 KiB
+// and the wrapper, with room); a stream that is longer fails on the device and is read on the host
+inline u64 inf_bound(u64 size) { return size + (size >> 12) + (size >> 14) + (size >> 25) + 13; }
+
+struct DevItem {
+    u64 key = ~0ull;  // pack << 48 | offset, or ~0: read by id
+    u64 data = 0;     // device class: where the stream starts in its pack
+    u64 size = 0;     // inflated size (host class: what the read gave)
+    u8 dev = 0;       // device class
+};
+}  // namespace
+
+extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, kd_blobs* out,
+                                        uint8_t* status, uint64_t stats[4]) {
+    if (!ctx || !odb || !out || (n && (!oids || !status))) { kd::set_error("kd_odb_read_batch_device: NULL"); return KD_EINVAL; }
+    out->n = n;
+    out->data = nullptr;
+    out->off = nullptr;
+    out->mem = KD_MEM_DEVICE;
+    out->size_hint = 0;
+    u64 st4[4] = {0, 0, 0, 0};
+    const int nt = default_threads(threads);
+    constexpr u64 CH = 256;
+    const u64 nch = (n + CH - 1) / CH;
+    std::lock_guard<std::mutex> dev_lock(odb->dev_mu);  // (the pinned staging is the store's)
+    std::vector<std::unique_ptr<Reader>> rds(nt);
+    auto reader = [&](int tid) -> Reader& {
+        if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
+        return *rds[tid];
+    };
+    // 1 + 2: every id located, its entry header parsed, its class decided
+    std::vector<DevItem> it(n);
+    par_items(nch, nt, [&](size_t c, int tid) {
+        Reader& rd = reader(tid);
+        for (u64 i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+            u64 o;
+            const long p = rd.locate(oids + 20 * i, &o);
+            if (p < 0 || p >= 0xFFFF || o >= (1ull << 48)) continue;
+            it[i].key = (u64)p << 48 | o;
+            int type;
+            u64 size, data, boff = 0;
+            const u8* boid = nullptr;
+            const Pack& pk = *odb->packs[p];
+            if (rd.entry_header(pk, o, &type, &size, &data, &boff, &boid) == RD_OK && type == OBJ_BLOB && size <= KD_INF_MAX &&
+                data < pk.pack.n - 20) {
+                it[i].dev = 1;
+                it[i].data = data;
+                it[i].size = size;
+            }
+        }
+    });
+    std::vector<u8> forced(n, 0);  // device items the device refused and the host could not read either
+    std::vector<u64> off(n + 1), soff(n + 1);
+    std::vector<u8> kind(n), dstat(n);
+    for (int pass = 0;; pass++) {
+        // host class: read by the Reader, threaded and in pack order (as kd_odb_read_batch reads)
+        std::vector<std::pair<u64, u64>> ord;
+        for (u64 i = 0; i < n; i++)
+            if (!it[i].dev || forced[i]) ord.push_back({it[i].key, i});
+        std::sort(ord.begin(), ord.end());
+        const u64 nh = ord.size(), nhch = (nh + CH - 1) / CH;
+        std::vector<std::vector<u8>> part(nhch);
+        std::vector<u64> at(n);
+        std::vector<u32> chunk_of(n);
+        par_items(nhch, nt, [&](size_t c, int tid) {
+            Reader& rd = reader(tid);
+            std::vector<u8> buf;
+            for (u64 s = c * CH; s < std::min(nh, (c + 1) * CH); s++) {
+                const u64 key = ord[s].first, i = ord[s].second;
+                int type = 0;
+                const int rc = key != ~0ull ? rd.read_packed(*odb->packs[key >> 48], key & ((1ull << 48) - 1), &type, buf)
+                                            : rd.read(oids + 20 * i, &type, buf);
+                status[i] = rc == RD_OK && type != OBJ_BLOB ? 2 : (u8)rc;
+                if (status[i]) buf.clear();
+                at[i] = part[c].size();
+                chunk_of[i] = (u32)c;
+                part[c].insert(part[c].end(), buf.begin(), buf.end());
+                it[i].size = buf.size();
+            }
+        });
+        // 3: sizes -> off; the sources' offsets (a device item's span is clipped to the pack's trailer)
+        off[0] = soff[0] = 0;
+        u64 ndev = 0, comp = 0;
+        for (u64 i = 0; i < n; i++) {
+            const bool dev = it[i].dev && !forced[i];
+            u64 span = it[i].size;
+            if (dev) {
+                const Pack& pk = *odb->packs[it[i].key >> 48];
+                span = std::min(inf_bound(it[i].size), pk.pack.n - 20 - it[i].data);
+                ndev++;
+                comp += span;
+            }
+            kind[i] = dev ? 0 : 1;
+            off[i + 1] = off[i] + it[i].size;
+            soff[i + 1] = soff[i] + span;
+        }
+        // 4: gather into the pinned staging (grow-only, 8 bytes of padding behind the last source).
+        // It holds every source of the call at once: about the arena's size, page-locked until the
+        // store is closed (kartdiff.h says so; chunking it through two buffers would bound it)
+        const u64 need = soff[n] + 8;
+        if (odb->pin_cap < need) {
+            if (odb->pin) kd_host_free(odb->pin);
+            odb->pin = nullptr;
+            odb->pin_cap = 0;
+            const u64 want = need + need / 4;
+            void* p = nullptr;
+            if (int rc = kd_host_alloc(want, &p)) return rc;
+            odb->pin = (u8*)p;
+            odb->pin_cap = want;
+        }
+        u8* pin = odb->pin;
+        par_items(nch, nt, [&](size_t c, int) {
+            for (u64 i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+                const u64 len = soff[i + 1] - soff[i];
+                if (!len) continue;
+                if (kind[i] == 0) memcpy(pin + soff[i], odb->packs[it[i].key >> 48]->pack.p + it[i].data, len);
+                else memcpy(pin + soff[i], part[chunk_of[i]].data() + at[i], len);
+            }
+        });
+        memset(pin + soff[n], 0, 8);
+        // 5: the arena and its offsets in HBM, one upload, one launch
+        void *d_data = nullptr, *d_off = nullptr;
+        int rc = kd_malloc(ctx, std::max<u64>(off[n], 16), &d_data);
+        if (!rc) rc = kd_malloc(ctx, 8 * (n + 1), &d_off);
+        if (!rc) rc = kd::inflate_from_host(ctx, pin, soff.data(), kind.data(), n, (u8*)d_data, off.data(), (u64*)d_off, dstat.data());
+        // 6: a device item with a nonzero status is read on the host: its bytes go into its place,
+        // or (the object is corrupt for the host too) it becomes a failed host item of another pass
+        u64 nfix = 0, nbad = 0;
+        if (!rc) {
+            Reader& rd = reader(0);
+            std::vector<u8> buf;
+            for (u64 i = 0; i < n && !rc; i++) {
+                if (kind[i] == 0) {
+                    status[i] = 0;
+                    if (dstat[i] == 0) continue;
+                    nfix++;
+                    int type = 0;
+                    const int hr = rd.read_packed(*odb->packs[it[i].key >> 48], it[i].key & ((1ull << 48) - 1), &type, buf);
+                    if (hr == RD_OK && type == OBJ_BLOB && buf.size() == it[i].size) {
+                        if (it[i].size) {
+                            rc = kd_memcpy(ctx, (u8*)d_data + off[i], buf.data(), it[i].size, KD_COPY_H2D);
+                            if (!rc) rc = kd_sync(ctx);  // (before buf is read into again; a rare path)
+                        }
+                    } else {
+                        forced[i] = 1;
+                        nbad++;
+                    }
+                } else if (dstat[i] != 0) {  // a raw copy cannot fail on ranges this function laid out
+                    kd::set_error("kd_odb_read_batch_device: raw item %llu: device status %u", (unsigned long long)i, dstat[i]);
+                    rc = KD_EINVAL;
+                }
+            }
+        }
+        st4[0] += ndev - nfix;
+        st4[2] += comp;
+        st4[3] += nfix;
+        if (rc || (nbad && pass == 0)) {
+            kd_mfree(ctx, d_data);
+            kd_mfree(ctx, d_off);
+            if (rc) return rc;
+            st4[0] = st4[2] = st4[3] = 0;  // the second pass counts again
+            continue;
+        }
+        if (nbad) { kd::set_error("kd_odb_read_batch_device: unreadable items after the host pass"); kd_mfree(ctx, d_data); kd_mfree(ctx, d_off); return KD_EINVAL; }
+        st4[1] = nh;
+        out->data = (const u8*)d_data;
+        out->off = (const u64*)d_off;
+        break;
+    }
+    if (stats) memcpy(stats, st4, sizeof st4);
     return KD_OK;
 }
 

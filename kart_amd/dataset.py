@@ -47,6 +47,10 @@ def _lap(name, t0):
         STAGE_TIMES[name] = STAGE_TIMES.get(name, 0.0) + (t1 - t0)
     return t1
 GPU_SORT_MIN = 1 << 20  # sides at least this long are sorted on the GPU when an engine is at hand
+# field_diff's blob read: True = the updates' blobs are inflated on the GPU into device arenas
+# (GitRepo.read_blobs_device) instead of read into host arenas and uploaded.  Off unless KD_DEVICE_INFLATE
+# says otherwise: measured, not assumed to win.
+DEVICE_INFLATE = os.environ.get("KD_DEVICE_INFLATE", "0") not in ("", "0")
 
 
 class Geometry(bytes):
@@ -444,7 +448,8 @@ def diff_feature(engine, base, target, feature_filter=None, reverse=False, updat
         # the updates' blobs are read on a worker thread (native, GIL released) while the deltas
         # are built here: field_diff then takes the arenas from updates.prefetch
         both = np.nonzero(has_a & has_b)[0]
-        if both.size >= PREFETCH_MIN_UPDATES:
+        # (not where field_diff's device route will read them: DEVICE_INFLATE and one repository)
+        if both.size >= PREFETCH_MIN_UPDATES and not (DEVICE_INFLATE and _device_source(old_v, new_v) is not None):
             updates.prefetch = _start_prefetch(old_v, new_v, old_leaf[both], new_leaf[both])
     old_pks, new_pks = _pk_column(old_v, a_idx, ia, n), _pk_column(new_v, b_idx, ib, n)
     t = _lap("pks", t)
@@ -677,7 +682,30 @@ def estimate_diff_feature_counts(engine, base_datasets, target_datasets, *, accu
     return counts
 
 
-def field_diff(engine, feature_diff, old_version, new_version, stats=None):
+def _device_source(old_v, new_v):
+    """the repository both versions read from, when it can read blobs into device arenas; else None"""
+    src = getattr(old_v._read_blobs, "source", None)
+    if src is None or src is not getattr(new_v._read_blobs, "source", None) or not hasattr(src, "read_blobs_device"):
+        return None
+    return src
+
+
+def _device_arenas(engine, old_v, new_v, old_leaf, new_leaf):
+    """the updates' blobs of both sides as two device arenas over one GitRepo.read_blobs_device
+    arena, with its counters — or None when the versions read from two repositories, or a blob is
+    missing (the host route then raises the reference's KeyError)"""
+    src = _device_source(old_v, new_v)
+    if src is None:
+        return None
+    oi, ni = np.asarray(old_leaf, np.int64), np.asarray(new_leaf, np.int64)
+    blobs, status, counters = src.read_blobs_device(engine, np.concatenate([old_v.oids[oi], new_v.oids[ni]]))
+    if status.any():
+        return None
+    k = oi.size
+    return blobs.view(0, k), blobs.view(k, k + ni.size), counters
+
+
+def field_diff(engine, feature_diff, old_version, new_version, stats=None, device_inflate=None):
     """Attach ``changed_fields`` (names, in _all_feature_keys order) to every update delta of
     ``feature_diff``, computed by kd_fielddiff in one batch.  Updates the GPU cannot handle
     (status != 0) get None and the caller uses the reference loop for them.
@@ -686,9 +714,19 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None):
     read by one kd_odb_read_batch straight into the arena kd_fielddiff takes (no per-blob Python
     object), and the arena is kept for later value reads.  Any other DeltaDiff (built by hand,
     combined with ``+``) goes through its lazy blobs.  ``stats`` (a dict) receives the seconds of
-    the blob reads, the kernel call and the name attachment."""
+    the blob reads, the kernel call and the name attachment.
+
+    ``device_inflate`` (None: ``DEVICE_INFLATE``): a live batch whose versions read from one repository
+    takes its blobs through ``read_blobs_device`` — inflated on the GPU into device arenas the kernel
+    reads in place.  No host arena is remembered then (later value reads take the per-blob path), and
+    ``stats["inflate"]`` holds the read's four counters.  A prefetch already pending is used as it is.
+    diff_feature starts that prefetch by the module flag alone (it cannot see this argument): with
+    ``DEVICE_INFLATE`` on and ``device_inflate=False`` here, versions of one repository are read on the
+    host without the overlap; versions of two repositories never had one."""
     import time
 
+    if device_inflate is None:
+        device_inflate = DEVICE_INFLATE
     t0 = time.perf_counter()
     with _gc_paused():
         batch = _live_batch(feature_diff, old_version, new_version)
@@ -697,9 +735,15 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None):
             n_ren = _attach_pk_fields(batch.renamed, old_version, new_version)
             if not ups:
                 return n_ren
+            dev = None
             if batch.prefetch is not None:  # read while the deltas were built (diff_feature)
                 fut, batch.prefetch = batch.prefetch, None
                 (od, oo), (nd, no) = fut.result()
+            elif device_inflate and (dev := _device_arenas(engine, old_version, new_version, batch.old_leaf,
+                                                           batch.new_leaf)) is not None:
+                (od, oo), (nd, no) = (dev[0], None), (dev[1], None)
+                if stats is not None:
+                    stats["inflate"] = dev[2]
             else:
                 (od, oo), (nd, no) = _arena_pair(old_version, new_version, batch.old_leaf, batch.new_leaf)
         else:

@@ -23,6 +23,13 @@ class DevBuf:
         self.ptr = p.value
 
     @classmethod
+    def adopt(cls, engine, ptr, nbytes):
+        """take over an allocation the library made with kd_malloc (freed like any other DevBuf)"""
+        b = cls.__new__(cls)
+        b.eng, b.nbytes, b.ptr = engine, int(nbytes), int(ptr)
+        return b
+
+    @classmethod
     def from_numpy(cls, engine, a):
         """device copy of a numpy array (synchronous; pinned staging is the caller's choice)"""
         a = np.ascontiguousarray(a)
@@ -164,15 +171,40 @@ class DevBlobs:
         self.data = DevBuf.from_numpy(engine, _nonempty(data, np.uint8))
         self.off = DevBuf.from_numpy(engine, off)
         self.nbytes = int(data.size)
+        self.host_off = np.ascontiguousarray(off, np.uint64)  # the offsets' host copy
+        self.off_at = 0  # index of this arena's first offset in ``off`` (a view starts further in)
         # typical blob = mean over the non-empty blobs (an arena may hold only the blobs a diff reads)
         nz = int(np.count_nonzero(off[1:] != off[:-1])) if self.n else 0
         self.mean_len = int((int(off[-1]) - int(off[0]) + nz - 1) // nz) if nz else 0
+
+    @classmethod
+    def adopt(cls, engine, data, off, host_off):
+        """an arena that is already in HBM: ``data`` / ``off`` DevBufs, ``host_off`` the offsets' host copy"""
+        b = cls.__new__(cls)
+        b.n = int(host_off.shape[0]) - 1
+        b.data, b.off, b.host_off, b.off_at = data, off, host_off, 0
+        b.nbytes = int(host_off[-1]) - int(host_off[0])
+        nz = int(np.count_nonzero(host_off[1:] != host_off[:-1])) if b.n else 0
+        b.mean_len = int((b.nbytes + nz - 1) // nz) if nz else 0
+        return b
+
+    def view(self, lo, hi):
+        """blobs lo .. hi as an arena of their own, over the same buffers"""
+        v = DevBlobs.adopt(None, self.data, self.off, self.host_off[lo:hi + 1])
+        v.off_at = self.off_at + lo
+        return v
+
+    def download(self):
+        """(data uint8, off uint64[n+1] from 0) on the host (tests, diagnosis)"""
+        ho = self.host_off
+        data = self.data.download(np.uint8, int(ho[-1]) - int(ho[0]), int(ho[0]))
+        return data, ho - ho[0]
 
     def kd_blobs(self):
         b = N.KdBlobs()
         b.n = self.n
         b.data = self.data.ptr
-        b.off = self.off.ptr
+        b.off = self.off.ptr + 8 * self.off_at
         b.mem = N.KD_MEM_DEVICE
         b.size_hint = min(self.mean_len, 0xFFFFFFFF)  # typical (mean) blob size: picks the window shape
         return b

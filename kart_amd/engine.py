@@ -319,21 +319,32 @@ class Engine:
         """Blob arenas (uint8 data, uint64 off[n+1]) per side; pairs uint32 [n, 2] (old blob,
         new blob) or None (blob u on both sides); maps: schema.FieldMaps; size_hint: the typical
         blob size in bytes (kd_blobs.size_hint; 0 = the arenas' mean), which picks the window shape.
+        A side may be a device.DevBlobs (an arena already in HBM, e.g. ObjectDB.read_batch_device's)
+        in place of its data, with None for its off.
         Returns (masks uint64 [n, words], status uint8 [n])."""
-        old_data = np.ascontiguousarray(old_data, np.uint8)
-        new_data = np.ascontiguousarray(new_data, np.uint8)
-        old_off = np.ascontiguousarray(old_off, np.uint64)
-        new_off = np.ascontiguousarray(new_off, np.uint64)
-        n = int(pairs.shape[0]) if pairs is not None else int(old_off.shape[0]) - 1
+        from .device import DevBlobs
+
+        sides, arrays = [], []  # (arrays: the converted host arrays, alive until the call has returned)
+        for d, o in ((old_data, old_off), (new_data, new_off)):
+            if isinstance(d, DevBlobs):
+                b = d.kd_blobs()
+                if size_hint:
+                    b.size_hint = int(size_hint)
+            else:
+                d = np.ascontiguousarray(d, np.uint8)
+                o = np.ascontiguousarray(o, np.uint64)
+                arrays += [d, o]
+                b = N.KdBlobs()
+                b.n = int(o.shape[0]) - 1
+                b.data = N.ptr(d) if d.size else N.ptr(_PAD)
+                b.off = N.ptr(o)
+                b.mem = N.KD_MEM_HOST
+                b.size_hint = int(size_hint)
+            sides.append(b)
+        ob, nb = sides
+        n = int(pairs.shape[0]) if pairs is not None else int(ob.n)
         if pairs is not None:
             pairs = np.ascontiguousarray(pairs, np.uint32)
-        ob, nb = N.KdBlobs(), N.KdBlobs()
-        for b, d, o in ((ob, old_data, old_off), (nb, new_data, new_off)):
-            b.n = int(o.shape[0]) - 1
-            b.data = N.ptr(d) if d.size else N.ptr(_PAD)
-            b.off = N.ptr(o)
-            b.mem = N.KD_MEM_HOST
-            b.size_hint = int(size_hint)
         masks = np.zeros((max(n, 1), maps.words), np.uint64)
         status = np.zeros(max(n, 1), np.uint8)
         km = maps.kd_maps()
@@ -343,6 +354,29 @@ class Engine:
             "kd_fielddiff",
         )
         return masks[:n], status[:n]
+
+    def inflate(self, src, src_off, dst_off, kind=None):
+        """zlib streams inflated on the GPU (kd_inflate_batch, host form): item i is
+        src[src_off[i]:src_off[i+1]] -> data[dst_off[i]:dst_off[i+1]], its inflated size the dst range
+        exactly; kind[i] = 1 copies the item as it is.  Returns (data uint8 [dst_off[-1]], status
+        uint8 [n] of KD_INF_* codes); a failed item's bytes are unspecified."""
+        src = np.ascontiguousarray(src, np.uint8)
+        src_off = np.ascontiguousarray(src_off, np.uint64)
+        dst_off = np.ascontiguousarray(dst_off, np.uint64)
+        n = int(src_off.shape[0]) - 1
+        if n < 0 or dst_off.shape[0] != n + 1:
+            raise ValueError("inflate: src_off and dst_off must hold n + 1 offsets")
+        if n and int(src_off[-1]) > src.size:
+            raise ValueError("inflate: src_off runs past src")
+        if kind is not None:
+            kind = np.ascontiguousarray(kind, np.uint8)
+            if kind.shape[0] != n:
+                raise ValueError("inflate: kind must hold n bytes")
+        data = np.zeros(max(int(dst_off[-1]), 1), np.uint8)
+        status = np.zeros(max(n, 1), np.uint8)
+        N.check(self.L.kd_inflate_batch(self.ctx, N.ptr(src) if src.size else N.ptr(_PAD), N.ptr(src_off), N.ptr(kind), n,
+                                        N.ptr(data), N.ptr(dst_off), N.ptr(status), N.KD_MEM_HOST), "kd_inflate_batch")
+        return data[:int(dst_off[-1])], status[:n]
 
     def merge3(self, ancestor, ours, theirs, flags=0) -> Merge3Result:
         """three PackedSides -> conflicts / merge deltas in path order (kd_merge3; sides packed on the

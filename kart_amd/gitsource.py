@@ -134,6 +134,14 @@ class GitRepo:
             data, off, status = self.odb.read_batch(oids)
         return data, off, status
 
+    def read_blobs_device(self, engine, oids):
+        """(DevBlobs, status, stats) of blobs [n, 20]: ``read_blobs`` with the arena in HBM, the plain
+        packed blobs inflated on the GPU (ObjectDB.read_batch_device)"""
+        blobs, status, stats = self.odb.read_batch_device(engine, oids)
+        if status.any() and self.odb.refresh():
+            blobs, status, stats = self.odb.read_batch_device(engine, oids)
+        return blobs, status, stats
+
     # ---- trees ----------------------------------------------------------------------------------
     def ls_tree(self, treeish):
         """one tree level: [(mode, type, oid hex, name)]"""

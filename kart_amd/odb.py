@@ -205,6 +205,29 @@ class ObjectDB:
         weakref.finalize(buf, self.L.kd_free, ctypes.c_void_p(addr))
         return np.frombuffer(buf, np.uint8), off, status[:n]
 
+    def read_batch_device(self, engine, oids, threads=0):
+        """``read_batch`` with the arena in HBM (kd_odb_read_batch_device): plain packed blobs are shipped
+        compressed and inflated on the GPU, everything else is read here and uploaded.  Returns
+        (device.DevBlobs, status uint8[n], stats) — the arena and status are what ``read_batch`` gives;
+        stats: ``device`` streams inflated on the GPU, ``host`` objects read here, ``compressed`` bytes
+        uploaded for the streams, ``fixups`` device items the host had to read after all."""
+        from .device import DevBlobs, DevBuf
+
+        oids = np.ascontiguousarray(oids, np.uint8).reshape(-1, 20)
+        n = oids.shape[0]
+        status = np.zeros(max(n, 1), np.uint8)
+        stats = np.zeros(4, np.uint64)
+        out = N.KdBlobs()
+        with self._lock:
+            N.check(self.L.kd_odb_read_batch_device(engine.ctx, self._h, oids.ctypes.data if n else None, n, threads,
+                                                    ctypes.byref(out), status.ctypes.data,
+                                                    stats.ctypes.data_as(N.c_u64p)), "kd_odb_read_batch_device")
+        off = DevBuf.adopt(engine, out.off, 8 * (n + 1))
+        host_off = off.download(np.uint64, n + 1)
+        data = DevBuf.adopt(engine, out.data, max(int(host_off[-1]), 16))
+        names = ("device", "host", "compressed", "fixups")
+        return DevBlobs.adopt(engine, data, off, host_off), status[:n], dict(zip(names, map(int, stats)))
+
     def walk(self, roots, subpath="", compare=None, threads=0):
         """Leaves under ``subpath`` of each root (commit/tag/tree ids), one Leaves per root.
         ``compare=(i, j)``: skip every entry identical in roots i and j (tree-OID pruning)."""
