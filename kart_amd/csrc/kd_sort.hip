@@ -619,7 +619,7 @@ __global__ __launch_bounds__(1024) void k_pkm_cscan(const u32* __restrict__ chun
     __shared__ u32 s_wave[1024 / 64];
     const int tid = threadIdx.x;
     u32 carry = 0;
-    for (u32 base = 0; base < nch; base += 1024 * PKC_PT) {  // (one pass up to 8192 chunks = 2^31 blocks)
+    for (u32 base = 0; base < nch; base += 1024 * PKC_PT) {  // (one pass up to 8192 chunks = 2^25 blocks = 2^31 pks)
         const u32 k0 = base + (u32)tid * PKC_PT;
         u32 v[PKC_PT], sum = 0;
 #pragma unroll

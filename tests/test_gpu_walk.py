@@ -45,7 +45,8 @@ def test_gpu_delta_pk_order_vs_numpy(engine, case):
     elif case == "spread":  # bitmap path, hundreds of scan chunks (the one-round-trip tail scan)
         u = np.unique(rng.integers(0, 200_000_000, 1_200_000, dtype=np.int64))
         pa, pb = u[: 2 * u.size // 3], u[u.size // 3:]
-    elif case == "range_1e9":  # bitmap path past the tail scan's register run (its looped form)
+    elif case == "range_1e9":  # bitmap path, 5,723 scan chunks: still one trip of the chunk totals' scan (8,192 chunks;
+        # its second trip is test_order_crafted.py's test_gpu_bitmap_two_trips)
         u = np.unique(rng.integers(0, 1_500_000_000, 600_000, dtype=np.int64))
         pa, pb = u[: 2 * u.size // 3], u[u.size // 3:]
     else:
