@@ -694,7 +694,10 @@ typedef struct kd_odb kd_odb;
 int kd_odb_open(const char* gitdir, kd_odb** out);
 /* Options of an object store (A/B switches; kd_odb_open seeds each from the environment variable in
  * brackets).  Unknown names: KD_EINVAL.
- *   zlib           [KD_ODB_ZLIB]       1: inflate with zlib even when libdeflate.so.0 is present */
+ *   zlib           [KD_ODB_ZLIB]       1: inflate with zlib even when libdeflate.so.0 is present
+ * Read-only (kd_odb_get_option), microseconds of the last kd_odb_read_batch_device_ex call with
+ * KD_RBD_DELTAS: rbd_plan_us (classes, forest, peeks, levels), rbd_peek_us (the header peeks in it),
+ * rbd_host_us (host reads, layout, gather), rbd_device_us (upload, launches, statuses back). */
 int kd_odb_set_option(kd_odb* odb, const char* name, int64_t value);
 int kd_odb_get_option(kd_odb* odb, const char* name, int64_t* value);
 int kd_odb_close(kd_odb* odb);
@@ -754,6 +757,52 @@ int kd_inflate_batch(kd_ctx* ctx, const uint8_t* src, const uint64_t* src_off, c
  * long as that takes. */
 int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, kd_blobs* out,
                              uint8_t* status, uint64_t stats[4]);
+
+/* -------- device deltas: git deltas applied on the GPU (opt-in route of the batched read) -------- */
+/* After a clone, fetch, gc or repack most feature blobs are OFS_DELTA / REF_DELTA entries against an
+ * earlier version of the same feature.  The decoder (kart_amd/csrc/kd_delta.h, written from git's pack
+ * format documentation) handles the two size varints, copy ops (up to 4 offset and 3 size bytes, size 0
+ * = 0x10000) and insert ops.  Status of one item: */
+#define KD_DL_OK 0u
+#define KD_DL_EHEADER 1u  /* a size varint truncated or longer than 10 bytes                          */
+#define KD_DL_EBASE 2u    /* base size != the base range's length                                     */
+#define KD_DL_ESIZE 3u    /* result size != the dst range's length                                    */
+#define KD_DL_EOP 4u      /* opcode 0                                                                 */
+#define KD_DL_ETRUNC 5u   /* an op's argument bytes or literals run past the delta                    */
+#define KD_DL_ECOPY 6u    /* a copy reaching past the base                                            */
+#define KD_DL_EOVER 7u    /* more output than the result size                                         */
+#define KD_DL_ESHORT 8u   /* delta exhausted before the result size                                   */
+#define KD_DL_EPARENT 9u  /* chained use: the base or the delta payload of this item did not come out OK */
+#define KD_DL_ERANGE 11u  /* device offsets that descend or leave their arena; base_idx[i] >= nb       */
+#define KD_DL_MAX_DEPTH 64u /* the deepest chain kd_odb_read_batch_device_ex rebuilds on the device   */
+/* One level of deltas: item i patches base[base_off[b] .. base_off[b+1]), b = base_idx[i] < nb (many items
+ * may share one base), with delta[delta_off[i] .. delta_off[i+1]) into dst[dst_off[i] .. dst_off[i+1]);
+ * status[i] = KD_DL_*.  The header's sizes must equal the base and dst ranges' lengths.  A failing item
+ * stops at its first error: the bytes of its own dst range are unspecified, nothing outside that range
+ * is written, and no byte outside the item's base and delta ranges is read.  One launch of k_dl_apply,
+ * 16 lanes per item.  base, delta and dst must not overlap.
+ * mem = KD_MEM_HOST: every array is host memory, staged by the library (workspace: the context's
+ * grow-only slots), offsets are checked (descending: KD_EINVAL) and the call returns with the results.
+ * mem = KD_MEM_DEVICE: every array is device memory and the call is queued on the context's stream. */
+int kd_delta_apply_batch(kd_ctx* ctx, const uint8_t* base, const uint64_t* base_off, uint64_t nb,
+                         const uint32_t* base_idx, const uint8_t* delta, const uint64_t* delta_off, uint64_t n,
+                         uint8_t* dst, const uint64_t* dst_off, uint8_t* status, uint32_t mem);
+/* kd_odb_read_batch_device with flags.  flags = 0 is kd_odb_read_batch_device itself (stats[4..7] = 0).
+ * KD_RBD_DELTAS: a requested OFS_DELTA / REF_DELTA object whose whole chain lies in its own pack, ends
+ * in a blob, is at most KD_DL_MAX_DEPTH links deep and has no stream or result above KD_INF_MAX is
+ * rebuilt on the device: the chain's base and every link's payload are inflated by k_inf_streams, then
+ * one k_dl_apply launch per level patches each link against its parent (results nobody requested and
+ * all payloads live in workspace).  The sizes a layout needs are read on the host by inflating at most
+ * the first 20 bytes of each link's payload.  A link that fails on the device fails every link below
+ * it; each requested one is read on the host and uploaded in place (a fixup).  out, status: as
+ * kd_odb_read_batch's, for every input.
+ * stats: [0] plain streams inflated on the device, [1] objects read on the host, [2] compressed bytes
+ * uploaded, [3] fixups, [4] requested objects rebuilt from a chain on the device, [5] unique delta links
+ * applied, [6] the deepest level launched, [7] workspace bytes (payloads and unrequested results);
+ * [0] + [4] + [1] + [3] == n. */
+#define KD_RBD_DELTAS 1u
+int kd_odb_read_batch_device_ex(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, uint32_t flags,
+                                kd_blobs* out, uint8_t* status, uint64_t stats[8]);
 /* A walk's leaves for one root, one block (kd_free): leaf i = path[path_off[i] .. path_off[i+1])
  * relative to the walked tree, '/'-separated, in git path order (what `git ls-tree -r` lists). */
 typedef struct kd_leaves {

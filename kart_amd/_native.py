@@ -39,6 +39,12 @@ KD_GF_EXACT = 0x4  # kd_geom_refine: decide what FP64 cannot certify in exact ar
 (KD_INF_OK, KD_INF_EHEADER, KD_INF_EBTYPE, KD_INF_ESTORED, KD_INF_ELENS, KD_INF_ESYMBOL, KD_INF_EDIST, KD_INF_EOVER,
  KD_INF_ESHORT, KD_INF_ESRC, KD_INF_EADLER, KD_INF_ERANGE) = range(12)
 KD_INF_MAX = 256 << 10  # the largest blob kd_odb_read_batch_device inflates on the device
+# kd_delta_apply_batch's status of one item (kartdiff.h KD_DL_*)
+(KD_DL_OK, KD_DL_EHEADER, KD_DL_EBASE, KD_DL_ESIZE, KD_DL_EOP, KD_DL_ETRUNC, KD_DL_ECOPY, KD_DL_EOVER, KD_DL_ESHORT,
+ KD_DL_EPARENT) = range(10)
+KD_DL_ERANGE = 11
+KD_DL_MAX_DEPTH = 64  # the deepest chain kd_odb_read_batch_device_ex rebuilds on the device
+KD_RBD_DELTAS = 1     # kd_odb_read_batch_device_ex flag: delta chains rebuilt on the device
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -398,6 +404,16 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(KdBlobs),
          ctypes.c_void_p, c_u64p],
+    ),
+    "kd_delta_apply_batch": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32],
+    ),
+    "kd_odb_read_batch_device_ex": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32,
+         ctypes.POINTER(KdBlobs), ctypes.c_void_p, c_u64p],
     ),
     "kd_walk": (
         ctypes.c_int,

@@ -20,16 +20,6 @@ namespace kd {
 
 constexpr int INF_LANES = 64;
 
-struct InfArgs {
-    const u8* src;
-    const u64* src_off;  // [n + 1]
-    const u8* kind;      // [n] or nullptr
-    u64 n;
-    u8* dst;
-    const u64* dst_off;  // [n + 1]
-    u8* status;
-};
-
 __global__ __launch_bounds__(INF_LANES) void k_inf_streams(InfArgs a) {
     __shared__ u32 lds[kd_inf::KD_INF_WORDS * INF_LANES];
     const u64 i = (u64)blockIdx.x * INF_LANES + threadIdx.x;

@@ -234,6 +234,19 @@ int gf_scan(kd_ctx* ctx, u32* cnt, u32 n, u64* total);
 // destroy the context's communicators (kd_fini)
 void comm_release(kd_ctx* ctx);
 
+// kd_inflate.hip: one launch of k_inf_streams on ctx->stream, every array device memory (kd_delta.hip
+// inflates chain bases and delta payloads into its workspace with it)
+struct InfArgs {
+    const u8* src;
+    const u64* src_off;  // [n + 1]
+    const u8* kind;      // [n] or nullptr
+    u64 n;
+    u8* dst;
+    const u64* dst_off;  // [n + 1]
+    u8* status;
+};
+int inflate_launch(kd_ctx* ctx, const InfArgs& a);
+
 // ---- classify2 (device form), kd_classify.hip ----
 // ordA / ordB (both or neither): the sides' OIDs and filename offsets are in another order, row
 // ord[i] belongs to sorted entry i (kd_diff2_device_perm)

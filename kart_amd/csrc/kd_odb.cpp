@@ -22,15 +22,18 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "kartdiff.h"
+#include "kd_delta.h"
 
 namespace kd {
 void set_error(const char* fmt, ...);
@@ -150,6 +153,8 @@ struct kd_odb {
     std::mutex dev_mu;
     u8* pin = nullptr;
     u64 pin_cap = 0;
+    // the last kd_odb_read_batch_device_ex call's host phases in microseconds (kd_odb_get_option "rbd_*_us")
+    int64_t rbd_us[4] = {0, 0, 0, 0};  // plan (all of it), peek (the header peeks in it), host reads + gather, device
 };
 
 namespace {
@@ -847,6 +852,13 @@ extern "C" int kd_odb_set_option(kd_odb* odb, const char* name, int64_t value) {
 
 extern "C" int kd_odb_get_option(kd_odb* odb, const char* name, int64_t* value) {
     if (!odb || !name || !value) { kd::set_error("kd_odb_get_option: NULL"); return KD_EINVAL; }
+    static const char* const rbd_names[4] = {"rbd_plan_us", "rbd_peek_us", "rbd_host_us", "rbd_device_us"};
+    for (int k = 0; k < 4; k++)
+        if (strcmp(name, rbd_names[k]) == 0) {
+            std::lock_guard<std::mutex> lk(odb->dev_mu);
+            *value = odb->rbd_us[k];
+            return KD_OK;
+        }
     if (strcmp(name, "zlib") != 0) { kd::set_error("kd_odb_get_option: unknown option '%s'", name); return KD_EINVAL; }
     *value = odb->zlib_only;
     return KD_OK;
@@ -961,7 +973,8 @@ extern "C" int kd_odb_read_batch(kd_odb* odb, const uint8_t* oids, uint64_t n, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// the batched read with the arena in HBM (kd_inflate.hip inflates the plain packed blobs)
+// the batched read with the arena in HBM (kd_inflate.hip inflates the plain packed blobs; with
+// KD_RBD_DELTAS kd_delta.hip rebuilds delta chains level by level from the plan made here)
 // ---------------------------------------------------------------------------------------------
 namespace kd {
 // kd_inflate.hip: upload the gathered sources, one launch of k_inf_streams, the status bytes back
@@ -978,13 +991,59 @@ struct DevItem {
     u64 key = ~0ull;  // pack << 48 | offset, or ~0: read by id
     u64 data = 0;     // device class: where the stream starts in its pack
     u64 size = 0;     // inflated size (host class: what the read gave)
-    u8 dev = 0;       // device class
+    u8 dev = 0;       // device class: 1 a plain stream, 2 (KD_RBD_DELTAS) rebuilt from its delta chain
+    u32 node = ~0u;   // KD_RBD_DELTAS: the entry's node in the delta forest, if it is one
 };
-}  // namespace
 
-extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, kd_blobs* out,
-                                        uint8_t* status, uint64_t stats[4]) {
-    if (!ctx || !odb || !out || (n && (!oids || !status))) { kd::set_error("kd_odb_read_batch_device: NULL"); return KD_EINVAL; }
+// One entry of the delta forest: a requested delta, or an ancestor of one (KD_RBD_DELTAS).
+struct DlNode {
+    u64 key = ~0ull;   // pack << 48 | offset
+    u64 pkey = ~0ull;  // the base's key (~0: a plain entry, the chain's root)
+    u64 data = 0;      // where the stream starts in its pack
+    u64 zsize = 0;     // the stream's inflated size (entry header)
+    u64 rsize = 0;     // the object's size
+    u64 bsize = 0;     // a delta: the base size its payload states
+    u32 parent = ~0u;
+    u32 level = 0;     // 0 for the plain base
+    u8 delta = 0;
+    u8 bad = 0;        // cannot be rebuilt on the device (the reason is the host route's to find)
+    u8 ok = 0;         // this entry and its whole chain can
+    // per pass
+    u8 in_ws = 0;      // the result lives in workspace (nobody requested it)
+    u64 at = 0;        // where the result is (arena or workspace) and where the payload is (workspace)
+    u64 pay = 0;
+    u32 st = 0, pst = 0;  // status indices of the result and of the payload
+};
+
+using Clock = std::chrono::steady_clock;
+inline int64_t us_since(Clock::time_point t0) {
+    return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(Clock::now() - t0).count();
+}
+
+// at most `cap` bytes from the front of the zlib stream at src (the Reader's z_stream: libdeflate
+// cannot stop early); *got <- how many came out
+bool peek_stream(Reader& rd, const u8* src, size_t avail, u8* out, size_t cap, size_t* got) {
+    *got = 0;
+    if (!rd.zok || inflateReset(&rd.z) != Z_OK) return false;
+    rd.z.next_in = (Bytef*)src;
+    rd.z.avail_in = (uInt)std::min<size_t>(avail, 0xFFFFFFFFu);
+    rd.z.next_out = out;
+    rd.z.avail_out = (uInt)cap;
+    const int r = inflate(&rd.z, Z_SYNC_FLUSH);
+    if (r != Z_OK && r != Z_STREAM_END && r != Z_BUF_ERROR) return false;
+    *got = cap - rd.z.avail_out;
+    return true;
+}
+
+u32 find_node(const std::vector<DlNode>& nodes, u64 key) {
+    auto it = std::lower_bound(nodes.begin(), nodes.end(), key, [](const DlNode& a, u64 k) { return a.key < k; });
+    return it != nodes.end() && it->key == key ? (u32)(it - nodes.begin()) : ~0u;
+}
+
+int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, uint32_t flags, kd_blobs* out,
+                           uint8_t* status, uint64_t st8[8]) {
+    const bool deltas = (flags & KD_RBD_DELTAS) != 0;
+    const auto t_start = Clock::now();
     out->n = n;
     out->data = nullptr;
     out->off = nullptr;
@@ -1002,6 +1061,44 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
     };
     // 1 + 2: every id located, its entry header parsed, its class decided
     std::vector<DevItem> it(n);
+    // KD_RBD_DELTAS: the entries of every requested delta's chain, found by the thread that meets them
+    // first (a thread stops walking up at an entry it has already listed: chains share their tails)
+    std::vector<std::unordered_set<u64>> seen(deltas ? nt : 0);
+    std::vector<std::vector<DlNode>> recs(deltas ? nt : 0);
+    auto discover = [&](Reader& rd, int tid, long p, u64 o) {
+        const Pack& pk = *odb->packs[p];
+        u64 cur = o;
+        for (int hop = 0; hop < MAX_CHAIN; hop++) {
+            DlNode nd;
+            nd.key = (u64)p << 48 | cur;
+            if (!seen[tid].insert(nd.key).second) return;
+            int t;
+            u64 sz, data, boff = 0;
+            const u8* boid = nullptr;
+            if (cur >= (1ull << 48) || rd.entry_header(pk, cur, &t, &sz, &data, &boff, &boid) != RD_OK || data >= pk.pack.n - 20 ||
+                sz > KD_INF_MAX) {
+                nd.bad = 1;
+                recs[tid].push_back(nd);
+                return;
+            }
+            nd.data = data;
+            nd.zsize = sz;
+            if (t == OBJ_OFS_DELTA) {
+                cur = boff;
+            } else if (t == OBJ_REF_DELTA) {
+                if (!pk.find(boid, &cur)) nd.bad = 1;  // the base is in another pack, loose, or nowhere
+            } else {
+                nd.rsize = sz;
+                nd.bad = t != OBJ_BLOB;
+                recs[tid].push_back(nd);
+                return;
+            }
+            nd.delta = 1;
+            if (!nd.bad) nd.pkey = (u64)p << 48 | cur;
+            recs[tid].push_back(nd);
+            if (nd.bad) return;
+        }
+    };
     par_items(nch, nt, [&](size_t c, int tid) {
         Reader& rd = reader(tid);
         for (u64 i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
@@ -1013,18 +1110,116 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
             u64 size, data, boff = 0;
             const u8* boid = nullptr;
             const Pack& pk = *odb->packs[p];
-            if (rd.entry_header(pk, o, &type, &size, &data, &boff, &boid) == RD_OK && type == OBJ_BLOB && size <= KD_INF_MAX &&
-                data < pk.pack.n - 20) {
+            if (rd.entry_header(pk, o, &type, &size, &data, &boff, &boid) != RD_OK) continue;
+            if (type == OBJ_BLOB && size <= KD_INF_MAX && data < pk.pack.n - 20) {
                 it[i].dev = 1;
                 it[i].data = data;
                 it[i].size = size;
+            } else if (deltas && (type == OBJ_OFS_DELTA || type == OBJ_REF_DELTA)) {
+                it[i].dev = 2;
+                discover(rd, tid, p, o);
             }
         }
     });
+    // the forest: unique entries in key order, parents linked, sizes peeked, levels and chains decided
+    std::vector<DlNode> nodes;
+    std::vector<u32> par;  // every entry's parent, apart from the entries (the walk up a chain touches nothing else)
+    int64_t peek_us = 0;
+    if (deltas) {
+        {
+            // (the keys are sorted, not the entries: 16 bytes move per comparison instead of a whole DlNode)
+            // and every thread's list on its own first, then merged pairwise)
+            std::vector<std::pair<u64, const DlNode*>> ks;
+            std::vector<size_t> seg{0};
+            for (auto& v : recs) {
+                for (const DlNode& nd : v) ks.push_back({nd.key, &nd});
+                seg.push_back(ks.size());
+            }
+            auto less = [](const auto& a, const auto& b) { return a.first < b.first; };
+            par_items(seg.size() - 1, nt, [&](size_t t, int) { std::sort(ks.begin() + seg[t], ks.begin() + seg[t + 1], less); });
+            while (seg.size() > 2) {
+                const size_t pairs = (seg.size() - 1) / 2;
+                par_items(pairs, nt, [&](size_t q, int) {
+                    std::inplace_merge(ks.begin() + seg[2 * q], ks.begin() + seg[2 * q + 1], ks.begin() + seg[2 * q + 2], less);
+                });
+                std::vector<size_t> next;
+                for (size_t q = 0; q < seg.size(); q += 2) next.push_back(seg[q]);
+                if (next.back() != seg.back()) next.push_back(seg.back());
+                seg.swap(next);
+            }
+            ks.erase(std::unique(ks.begin(), ks.end(), [](const auto& a, const auto& b) { return a.first == b.first; }), ks.end());
+            nodes.resize(ks.size());
+            par_items((ks.size() + CH - 1) / CH, nt, [&](size_t c, int) {
+                for (u64 k = c * CH; k < std::min<u64>(ks.size(), (c + 1) * CH); k++) nodes[k] = *ks[k].second;
+            });
+        }
+        const u64 nn = nodes.size(), nnch = (nn + CH - 1) / CH;
+        // a delta's result size and its base's are the two varints at the front of its inflated payload
+        const auto t_peek = Clock::now();
+        par_items(nnch, nt, [&](size_t c, int tid) {
+            Reader& rd = reader(tid);
+            for (u64 k = c * CH; k < std::min(nn, (c + 1) * CH); k++) {
+                DlNode& nd = nodes[k];
+                if (!nd.delta || nd.bad) continue;
+                nd.parent = find_node(nodes, nd.pkey);
+                const Pack& pk = *odb->packs[nd.key >> 48];
+                u8 hb[20];
+                size_t got = 0, pos = 0;
+                if (nd.parent == ~0u || !peek_stream(rd, pk.pack.p + nd.data, pk.pack.n - 20 - nd.data, hb, (size_t)std::min<u64>(20, nd.zsize), &got) ||
+                    !kd_dl::size_varint(hb, got, &pos, &nd.bsize) || !kd_dl::size_varint(hb, got, &pos, &nd.rsize) || nd.rsize > KD_INF_MAX)
+                    nd.bad = 1;
+            }
+        });
+        peek_us = us_since(t_peek);
+        std::vector<u8> state(nn, 0);  // 1 on the stack, 2 decided
+        std::vector<u32> stack;
+        for (u64 s = 0; s < nn; s++) {
+            stack.clear();
+            for (u32 c = (u32)s; state[c] == 0;) {
+                state[c] = 1;
+                stack.push_back(c);
+                if (nodes[c].parent == ~0u) break;
+                c = nodes[c].parent;
+            }
+            for (size_t k = stack.size(); k-- > 0;) {
+                DlNode& nd = nodes[stack[k]];
+                if (!nd.delta) {
+                    nd.ok = !nd.bad;
+                } else if (!nd.bad && state[nd.parent] == 2) {  // (a parent still on the stack: a cycle of REF_DELTAs)
+                    const DlNode& pa = nodes[nd.parent];
+                    nd.level = pa.level + 1;
+                    nd.ok = pa.ok && nd.bsize == pa.rsize && nd.level <= KD_DL_MAX_DEPTH;
+                }
+                state[stack[k]] = 2;
+            }
+        }
+        par_items(nch, nt, [&](size_t c, int) {
+            for (u64 i = c * CH; i < std::min(n, (c + 1) * CH); i++) {
+                if (!it[i].dev) continue;
+                it[i].node = find_node(nodes, it[i].key);
+                if (it[i].dev == 2) {
+                    if (it[i].node != ~0u && nodes[it[i].node].ok) it[i].size = nodes[it[i].node].rsize;
+                    else it[i].dev = 0;  // host class: the host route gives it its bytes or its status
+                }
+            }
+        });
+        par.resize(nn);
+        for (u64 k = 0; k < nn; k++) par[k] = nodes[k].parent;
+    }
+    const int64_t plan_us = us_since(t_start);
+    int64_t host_us = 0, device_us = 0;
+    std::vector<u64> soff2, woff, level_start;
+    std::vector<kd::DlItem> ditems;
+    std::vector<kd::DlCopy> copies;
+    std::vector<u32> wsitem;
+    std::vector<u8> need;          // per pass: the entry is on a delta-class request's chain
+    std::vector<int64_t> home;     // per pass: the first request that names the entry
+    std::vector<u8> hst;
     std::vector<u8> forced(n, 0);  // device items the device refused and the host could not read either
     std::vector<u64> off(n + 1), soff(n + 1);
     std::vector<u8> kind(n), dstat(n);
     for (int pass = 0;; pass++) {
+        const auto t_pass = Clock::now();
         // host class: read by the Reader, threaded and in pack order (as kd_odb_read_batch reads)
         std::vector<std::pair<u64, u64>> ord;
         for (u64 i = 0; i < n; i++)
@@ -1054,22 +1249,124 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
         off[0] = soff[0] = 0;
         u64 ndev = 0, comp = 0;
         for (u64 i = 0; i < n; i++) {
-            const bool dev = it[i].dev && !forced[i];
+            const u8 cls = forced[i] ? 0 : it[i].dev;
             u64 span = it[i].size;
-            if (dev) {
+            if (cls == 1) {
                 const Pack& pk = *odb->packs[it[i].key >> 48];
                 span = std::min(inf_bound(it[i].size), pk.pack.n - 20 - it[i].data);
                 ndev++;
                 comp += span;
+            } else if (cls == 2) {
+                span = 0;  // (rebuilt by k_dl_apply: a raw item without a source, which the inflate launch leaves alone)
             }
-            kind[i] = dev ? 0 : 1;
+            kind[i] = cls == 1 ? 0 : cls == 2 ? 2 : 1;
             off[i + 1] = off[i] + it[i].size;
             soff[i + 1] = soff[i] + span;
+        }
+        // KD_RBD_DELTAS: the levels.  Needed entries: every delta-class request's chain.  An entry's home is
+        // the first request that names it; one nobody requested lives in workspace, as every payload does
+        u64 m = 0, ws_bytes = 0, ndelta = 0;
+        u32 depth = 0;
+        if (deltas) {
+            const u64 nn = nodes.size();
+            need.assign(nn, 0);
+            home.assign(nn, -1);
+            copies.clear();
+            for (u64 i = 0; i < n; i++) {
+                if (kind[i] != 2) continue;
+                ndelta++;
+                for (u32 k = it[i].node; k != ~0u && !need[k]; k = par[k]) need[k] = 1;
+            }
+            for (u64 i = 0; i < n; i++) {
+                if (kind[i] == 1 || it[i].node == ~0u || !need[it[i].node]) continue;
+                int64_t& h = home[it[i].node];
+                if (h < 0) h = (int64_t)i;
+                else if (kind[i] == 2) copies.push_back({0, off[i], it[i].size, 0, (u32)h});  // (src: the home, below)
+            }
+            // launch 2's items: unrequested chain bases, then every payload; unrequested results behind them.
+            // Entries are taken in key order, which is pack order: neighbours in a launch are neighbours in the pack
+            wsitem.clear();
+            for (u64 k = 0; k < nn; k++)
+                if (need[k] && !nodes[k].delta && home[k] < 0) wsitem.push_back((u32)k);
+            const u64 nbase = wsitem.size();
+            for (u64 k = 0; k < nn; k++)
+                if (need[k] && nodes[k].delta) {
+                    wsitem.push_back((u32)k);
+                    depth = std::max(depth, nodes[k].level);
+                }
+            m = wsitem.size();
+            soff2.assign(m + 1, 0);
+            woff.assign(m + 1, 0);
+            for (u64 j = 0; j < m; j++) {
+                DlNode& nd = nodes[wsitem[j]];
+                const Pack& pk = *odb->packs[nd.key >> 48];
+                soff2[j + 1] = soff2[j] + std::min(inf_bound(nd.zsize), pk.pack.n - 20 - nd.data);
+                woff[j + 1] = woff[j] + nd.zsize;
+                if (j < nbase) {
+                    nd.in_ws = 1;
+                    nd.at = woff[j];
+                    nd.st = (u32)(n + j);
+                } else {
+                    nd.pay = woff[j];
+                    nd.pst = (u32)(n + j);
+                }
+            }
+            comp += soff2[m];
+            ws_bytes = woff[m];
+            // the delta entries in level order
+            level_start.assign(depth + 2, 0);
+            for (u64 j = nbase; j < m; j++) level_start[nodes[wsitem[j]].level + 1]++;
+            for (u32 l = 1; l <= depth + 1; l++) level_start[l] += level_start[l - 1];
+            ditems.assign(m - nbase, kd::DlItem{});
+            std::vector<u64> fill(level_start.begin(), level_start.end());
+            std::vector<u32> order(m - nbase);
+            for (u64 j = nbase; j < m; j++) order[fill[nodes[wsitem[j]].level]++] = wsitem[j];
+            for (u64 j = 0; j < order.size(); j++) {
+                DlNode& nd = nodes[order[j]];
+                nd.st = (u32)(n + m + j);
+                nd.in_ws = home[order[j]] < 0;
+                if (nd.in_ws) {
+                    nd.at = ws_bytes;
+                    ws_bytes += nd.rsize;
+                } else {
+                    nd.at = off[home[order[j]]];
+                }
+            }
+            for (u64 k = 0; k < nn; k++)
+                if (need[k] && !nodes[k].delta && home[k] >= 0) {
+                    nodes[k].in_ws = 0;
+                    nodes[k].at = off[home[k]];
+                    nodes[k].st = (u32)home[k];
+                }
+            for (u64 j = 0; j < order.size(); j++) {
+                const DlNode& nd = nodes[order[j]];
+                const DlNode& pa = nodes[nd.parent];
+                kd::DlItem& d = ditems[j];
+                d.base_at = pa.at;
+                d.delta_at = nd.pay;
+                d.dst_at = nd.at;
+                d.base_len = (u32)pa.rsize;
+                d.delta_len = (u32)nd.zsize;
+                d.dst_len = (u32)nd.rsize;
+                d.where = (pa.in_ws ? 1u : 0u) | 2u | (nd.in_ws ? 4u : 0u);
+                d.base_st = pa.st;
+                d.delta_st = nd.pst;
+                d.out_st = nd.st;
+            }
+            for (kd::DlCopy& c : copies) {
+                const DlNode& nd = nodes[it[c.pad].node];  // (pad carried the home request)
+                c.src_at = nd.at;
+                c.src_ws = 0;
+                c.pad = 0;
+            }
+            // level_start as delta_read_from_host takes it: [l - 1] .. [l] is level l
+            level_start.erase(level_start.begin());
+            hst.assign(n + m + ditems.size(), 0);
         }
         // 4: gather into the pinned staging (grow-only, 8 bytes of padding behind the last source).
         // It holds every source of the call at once: about the arena's size, page-locked until the
         // store is closed (kartdiff.h says so; chunking it through two buffers would bound it)
-        const u64 need = soff[n] + 8;
+        const u64 need = soff[n] + (deltas ? soff2[m] : 0) + 8;
         if (odb->pin_cap < need) {
             if (odb->pin) kd_host_free(odb->pin);
             odb->pin = nullptr;
@@ -1089,15 +1386,57 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
                 else memcpy(pin + soff[i], part[chunk_of[i]].data() + at[i], len);
             }
         });
-        memset(pin + soff[n], 0, 8);
-        // 5: the arena and its offsets in HBM, one upload, one launch
+        if (deltas) {
+            const u64 mch = (m + CH - 1) / CH;
+            par_items(mch, nt, [&](size_t c, int) {
+                for (u64 j = c * CH; j < std::min(m, (c + 1) * CH); j++) {
+                    const DlNode& nd = nodes[wsitem[j]];
+                    memcpy(pin + soff[n] + soff2[j], odb->packs[nd.key >> 48]->pack.p + nd.data, soff2[j + 1] - soff2[j]);
+                }
+            });
+        }
+        memset(pin + need - 8, 0, 8);
+        host_us += us_since(t_pass);
+        const auto t_dev = Clock::now();
+        // 5: the arena and its offsets in HBM, one upload, one launch (KD_RBD_DELTAS: two, and one per level)
         void *d_data = nullptr, *d_off = nullptr;
         int rc = kd_malloc(ctx, std::max<u64>(off[n], 16), &d_data);
         if (!rc) rc = kd_malloc(ctx, 8 * (n + 1), &d_off);
-        if (!rc) rc = kd::inflate_from_host(ctx, pin, soff.data(), kind.data(), n, (u8*)d_data, off.data(), (u64*)d_off, dstat.data());
+        if (!rc && !deltas)
+            rc = kd::inflate_from_host(ctx, pin, soff.data(), kind.data(), n, (u8*)d_data, off.data(), (u64*)d_off, dstat.data());
+        if (!rc && deltas) {
+            for (u64 i = 0; i < n; i++) kind[i] = kind[i] != 0;  // (what k_inf_streams takes)
+            kd::DlPlan pl{};
+            pl.h_src = pin;
+            pl.n = n;
+            pl.soff1 = soff.data();
+            pl.kind1 = kind.data();
+            pl.off = off.data();
+            pl.m = m;
+            pl.soff2 = soff2.data();
+            pl.woff = woff.data();
+            pl.ws_bytes = ws_bytes;
+            pl.items = ditems.data();
+            pl.n_items = ditems.size();
+            pl.level_start = level_start.data();
+            pl.depth = depth;
+            pl.copies = copies.data();
+            pl.n_copies = copies.size();
+            pl.h_status = hst.data();
+            pl.d_dst = (u8*)d_data;
+            pl.d_dst_off = (u64*)d_off;
+            rc = kd::delta_read_from_host(ctx, pl);
+            // a request's device status: its own inflate's, or its entry's after the levels
+            for (u64 i = 0; i < n && !rc; i++) {
+                const bool dl = !forced[i] && it[i].dev == 2;
+                dstat[i] = dl ? hst[nodes[it[i].node].st] : hst[i];
+                if (dl) kind[i] = 0;  // (below: a device item)
+            }
+        }
+        device_us += us_since(t_dev);
         // 6: a device item with a nonzero status is read on the host: its bytes go into its place,
         // or (the object is corrupt for the host too) it becomes a failed host item of another pass
-        u64 nfix = 0, nbad = 0;
+        u64 nfix = 0, nfixd = 0, nbad = 0;
         if (!rc) {
             Reader& rd = reader(0);
             std::vector<u8> buf;
@@ -1106,6 +1445,7 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
                     status[i] = 0;
                     if (dstat[i] == 0) continue;
                     nfix++;
+                    if (!forced[i] && it[i].dev == 2) nfixd++;
                     int type = 0;
                     const int hr = rd.read_packed(*odb->packs[it[i].key >> 48], it[i].key & ((1ull << 48) - 1), &type, buf);
                     if (hr == RD_OK && type == OBJ_BLOB && buf.size() == it[i].size) {
@@ -1123,7 +1463,7 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
                 }
             }
         }
-        st4[0] += ndev - nfix;
+        st4[0] += ndev - (nfix - nfixd);
         st4[2] += comp;
         st4[3] += nfix;
         if (rc || (nbad && pass == 0)) {
@@ -1137,10 +1477,41 @@ extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t*
         st4[1] = nh;
         out->data = (const u8*)d_data;
         out->off = (const u64*)d_off;
+        memcpy(st8, st4, sizeof st4);
+        st8[4] = ndelta - nfixd;
+        st8[5] = ditems.size();
+        st8[6] = depth;
+        st8[7] = ws_bytes;
         break;
     }
-    if (stats) memcpy(stats, st4, sizeof st4);
+    if (deltas) {
+        odb->rbd_us[0] = plan_us;
+        odb->rbd_us[1] = peek_us;
+        odb->rbd_us[2] = host_us;
+        odb->rbd_us[3] = device_us;
+    }
     return KD_OK;
+}
+}  // namespace
+
+extern "C" int kd_odb_read_batch_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, kd_blobs* out,
+                                        uint8_t* status, uint64_t stats[4]) {
+    if (!ctx || !odb || !out || (n && (!oids || !status))) { kd::set_error("kd_odb_read_batch_device: NULL"); return KD_EINVAL; }
+    u64 st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int rc = read_batch_device_impl(ctx, odb, oids, n, threads, 0, out, status, st8);
+    if (!rc && stats) memcpy(stats, st8, 4 * sizeof(u64));
+    return rc;
+}
+
+extern "C" int kd_odb_read_batch_device_ex(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, uint32_t flags,
+                                           kd_blobs* out, uint8_t* status, uint64_t stats[8]) {
+    if (!ctx || !odb || !out || (n && (!oids || !status))) { kd::set_error("kd_odb_read_batch_device_ex: NULL"); return KD_EINVAL; }
+    if (flags & ~KD_RBD_DELTAS) { kd::set_error("kd_odb_read_batch_device_ex: unknown flags %u", flags); return KD_EINVAL; }
+    if (n >= (1ull << 30)) { kd::set_error("kd_odb_read_batch_device_ex: too many ids"); return KD_EINVAL; }
+    u64 st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int rc = read_batch_device_impl(ctx, odb, oids, n, threads, flags, out, status, st8);
+    if (!rc && stats) memcpy(stats, st8, sizeof st8);
+    return rc;
 }
 
 extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* subpath, int cmp0, int cmp1, int threads,

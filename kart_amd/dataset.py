@@ -51,6 +51,10 @@ GPU_SORT_MIN = 1 << 20  # sides at least this long are sorted on the GPU when an
 # (GitRepo.read_blobs_device) instead of read into host arenas and uploaded.  Off unless KD_DEVICE_INFLATE
 # says otherwise: measured, not assumed to win.
 DEVICE_INFLATE = os.environ.get("KD_DEVICE_INFLATE", "0") not in ("", "0")
+# ... and on that route: True = OFS_DELTA / REF_DELTA blobs (a cloned, gc'd or repacked repository's) are
+# rebuilt on the GPU from their chains instead of read on the host and uploaded.  Off unless
+# KD_DEVICE_DELTAS says otherwise.
+DEVICE_DELTAS = os.environ.get("KD_DEVICE_DELTAS", "0") not in ("", "0")
 
 
 class Geometry(bytes):
@@ -690,7 +694,7 @@ def _device_source(old_v, new_v):
     return src
 
 
-def _device_arenas(engine, old_v, new_v, old_leaf, new_leaf):
+def _device_arenas(engine, old_v, new_v, old_leaf, new_leaf, deltas=False):
     """the updates' blobs of both sides as two device arenas over one GitRepo.read_blobs_device
     arena, with its counters — or None when the versions read from two repositories, or a blob is
     missing (the host route then raises the reference's KeyError)"""
@@ -698,14 +702,16 @@ def _device_arenas(engine, old_v, new_v, old_leaf, new_leaf):
     if src is None:
         return None
     oi, ni = np.asarray(old_leaf, np.int64), np.asarray(new_leaf, np.int64)
-    blobs, status, counters = src.read_blobs_device(engine, np.concatenate([old_v.oids[oi], new_v.oids[ni]]))
+    oids = np.concatenate([old_v.oids[oi], new_v.oids[ni]])
+    # (the keyword only when asked for: a source without the option still serves the plain route)
+    blobs, status, counters = src.read_blobs_device(engine, oids, deltas=True) if deltas else src.read_blobs_device(engine, oids)
     if status.any():
         return None
     k = oi.size
     return blobs.view(0, k), blobs.view(k, k + ni.size), counters
 
 
-def field_diff(engine, feature_diff, old_version, new_version, stats=None, device_inflate=None):
+def field_diff(engine, feature_diff, old_version, new_version, stats=None, device_inflate=None, device_deltas=None):
     """Attach ``changed_fields`` (names, in _all_feature_keys order) to every update delta of
     ``feature_diff``, computed by kd_fielddiff in one batch.  Updates the GPU cannot handle
     (status != 0) get None and the caller uses the reference loop for them.
@@ -720,6 +726,8 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None, devic
     takes its blobs through ``read_blobs_device`` — inflated on the GPU into device arenas the kernel
     reads in place.  No host arena is remembered then (later value reads take the per-blob path), and
     ``stats["inflate"]`` holds the read's four counters.  A prefetch already pending is used as it is.
+    ``device_deltas`` (None: ``DEVICE_DELTAS``) is consulted only when that route is taken: delta chains
+    are rebuilt on the GPU too, and ``stats["inflate"]`` then holds the read's eight counters.
     diff_feature starts that prefetch by the module flag alone (it cannot see this argument): with
     ``DEVICE_INFLATE`` on and ``device_inflate=False`` here, versions of one repository are read on the
     host without the overlap; versions of two repositories never had one."""
@@ -727,6 +735,8 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None, devic
 
     if device_inflate is None:
         device_inflate = DEVICE_INFLATE
+    if device_deltas is None:
+        device_deltas = DEVICE_DELTAS
     t0 = time.perf_counter()
     with _gc_paused():
         batch = _live_batch(feature_diff, old_version, new_version)
@@ -740,7 +750,7 @@ def field_diff(engine, feature_diff, old_version, new_version, stats=None, devic
                 fut, batch.prefetch = batch.prefetch, None
                 (od, oo), (nd, no) = fut.result()
             elif device_inflate and (dev := _device_arenas(engine, old_version, new_version, batch.old_leaf,
-                                                           batch.new_leaf)) is not None:
+                                                           batch.new_leaf, bool(device_deltas))) is not None:
                 (od, oo), (nd, no) = (dev[0], None), (dev[1], None)
                 if stats is not None:
                     stats["inflate"] = dev[2]

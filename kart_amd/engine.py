@@ -378,6 +378,31 @@ class Engine:
                                         N.ptr(data), N.ptr(dst_off), N.ptr(status), N.KD_MEM_HOST), "kd_inflate_batch")
         return data[:int(dst_off[-1])], status[:n]
 
+    def apply_deltas(self, base, base_off, base_idx, delta, delta_off, dst_off):
+        """one level of git deltas applied on the GPU (kd_delta_apply_batch, host form): item i patches
+        base[base_off[b]:base_off[b+1]], b = base_idx[i], with delta[delta_off[i]:delta_off[i+1]] into
+        data[dst_off[i]:dst_off[i+1]]; the delta's two sizes must be the base and dst ranges' lengths.
+        Returns (data uint8 [dst_off[-1]], status uint8 [n] of KD_DL_* codes); a failed item's bytes are
+        unspecified."""
+        base = np.ascontiguousarray(base, np.uint8)
+        delta = np.ascontiguousarray(delta, np.uint8)
+        base_off = np.ascontiguousarray(base_off, np.uint64)
+        base_idx = np.ascontiguousarray(base_idx, np.uint32)
+        delta_off = np.ascontiguousarray(delta_off, np.uint64)
+        dst_off = np.ascontiguousarray(dst_off, np.uint64)
+        n, nb = int(delta_off.shape[0]) - 1, int(base_off.shape[0]) - 1
+        if n < 0 or nb < 0 or dst_off.shape[0] != n + 1 or base_idx.shape[0] != n:
+            raise ValueError("apply_deltas: delta_off and dst_off must hold n + 1 offsets, base_idx n, base_off nb + 1")
+        if int(base_off[-1]) > base.size or int(delta_off[-1]) > delta.size:
+            raise ValueError("apply_deltas: offsets run past their arena")
+        data = np.zeros(max(int(dst_off[-1]), 1), np.uint8)
+        status = np.zeros(max(n, 1), np.uint8)
+        N.check(self.L.kd_delta_apply_batch(self.ctx, N.ptr(base) if base.size else N.ptr(_PAD), N.ptr(base_off), nb,
+                                            N.ptr(base_idx) if n else N.ptr(_PAD), N.ptr(delta) if delta.size else N.ptr(_PAD),
+                                            N.ptr(delta_off), n, N.ptr(data), N.ptr(dst_off), N.ptr(status), N.KD_MEM_HOST),
+                "kd_delta_apply_batch")
+        return data[:int(dst_off[-1])], status[:n]
+
     def merge3(self, ancestor, ours, theirs, flags=0) -> Merge3Result:
         """three PackedSides -> conflicts / merge deltas in path order (kd_merge3; sides packed on the
         GPU with walk-order rows through kd_merge3_device_perm)"""

@@ -134,12 +134,13 @@ class GitRepo:
             data, off, status = self.odb.read_batch(oids)
         return data, off, status
 
-    def read_blobs_device(self, engine, oids):
+    def read_blobs_device(self, engine, oids, deltas=False):
         """(DevBlobs, status, stats) of blobs [n, 20]: ``read_blobs`` with the arena in HBM, the plain
-        packed blobs inflated on the GPU (ObjectDB.read_batch_device)"""
-        blobs, status, stats = self.odb.read_batch_device(engine, oids)
+        packed blobs inflated on the GPU (ObjectDB.read_batch_device); ``deltas``: delta chains rebuilt
+        there too"""
+        blobs, status, stats = self.odb.read_batch_device(engine, oids, deltas=deltas)
         if status.any() and self.odb.refresh():
-            blobs, status, stats = self.odb.read_batch_device(engine, oids)
+            blobs, status, stats = self.odb.read_batch_device(engine, oids, deltas=deltas)
         return blobs, status, stats
 
     # ---- trees ----------------------------------------------------------------------------------

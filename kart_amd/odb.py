@@ -205,27 +205,36 @@ class ObjectDB:
         weakref.finalize(buf, self.L.kd_free, ctypes.c_void_p(addr))
         return np.frombuffer(buf, np.uint8), off, status[:n]
 
-    def read_batch_device(self, engine, oids, threads=0):
+    def read_batch_device(self, engine, oids, threads=0, deltas=False):
         """``read_batch`` with the arena in HBM (kd_odb_read_batch_device): plain packed blobs are shipped
         compressed and inflated on the GPU, everything else is read here and uploaded.  Returns
         (device.DevBlobs, status uint8[n], stats) — the arena and status are what ``read_batch`` gives;
         stats: ``device`` streams inflated on the GPU, ``host`` objects read here, ``compressed`` bytes
-        uploaded for the streams, ``fixups`` device items the host had to read after all."""
+        uploaded for the streams, ``fixups`` device items the host had to read after all.
+        ``deltas=True`` (kd_odb_read_batch_device_ex, KD_RBD_DELTAS): OFS_DELTA / REF_DELTA blobs whose
+        chain lies in their own pack are rebuilt on the GPU too, level by level; stats then also holds
+        ``deltas`` requested objects rebuilt from a chain, ``links`` unique delta entries applied,
+        ``depth`` the deepest level launched and ``scratch`` workspace bytes."""
         from .device import DevBlobs, DevBuf
 
         oids = np.ascontiguousarray(oids, np.uint8).reshape(-1, 20)
         n = oids.shape[0]
         status = np.zeros(max(n, 1), np.uint8)
-        stats = np.zeros(4, np.uint64)
+        stats = np.zeros(8 if deltas else 4, np.uint64)
         out = N.KdBlobs()
         with self._lock:
-            N.check(self.L.kd_odb_read_batch_device(engine.ctx, self._h, oids.ctypes.data if n else None, n, threads,
-                                                    ctypes.byref(out), status.ctypes.data,
-                                                    stats.ctypes.data_as(N.c_u64p)), "kd_odb_read_batch_device")
+            if deltas:
+                N.check(self.L.kd_odb_read_batch_device_ex(engine.ctx, self._h, oids.ctypes.data if n else None, n, threads,
+                                                           N.KD_RBD_DELTAS, ctypes.byref(out), status.ctypes.data,
+                                                           stats.ctypes.data_as(N.c_u64p)), "kd_odb_read_batch_device_ex")
+            else:
+                N.check(self.L.kd_odb_read_batch_device(engine.ctx, self._h, oids.ctypes.data if n else None, n, threads,
+                                                        ctypes.byref(out), status.ctypes.data,
+                                                        stats.ctypes.data_as(N.c_u64p)), "kd_odb_read_batch_device")
         off = DevBuf.adopt(engine, out.off, 8 * (n + 1))
         host_off = off.download(np.uint64, n + 1)
         data = DevBuf.adopt(engine, out.data, max(int(host_off[-1]), 16))
-        names = ("device", "host", "compressed", "fixups")
+        names = ("device", "host", "compressed", "fixups", "deltas", "links", "depth", "scratch")
         return DevBlobs.adopt(engine, data, off, host_off), status[:n], dict(zip(names, map(int, stats)))
 
     def walk(self, roots, subpath="", compare=None, threads=0):
