@@ -695,6 +695,9 @@ int kd_odb_open(const char* gitdir, kd_odb** out);
 /* Options of an object store (A/B switches; kd_odb_open seeds each from the environment variable in
  * brackets).  Unknown names: KD_EINVAL.
  *   zlib           [KD_ODB_ZLIB]       1: inflate with zlib even when libdeflate.so.0 is present
+ *   walk_batch_bytes [KD_WALK_BATCH_BYTES]  kd_walk_device reads its leaf trees in batches of about this many
+ *                  compressed and host-read bytes (default 64 MiB): the bound of a walk's pinned staging and
+ *                  device arena.  A batch always holds at least one task.
  * Read-only (kd_odb_get_option), microseconds of the last kd_odb_read_batch_device_ex call with
  * KD_RBD_DELTAS: rbd_plan_us (classes, forest, peeks, levels), rbd_peek_us (the header peeks in it),
  * rbd_host_us (host reads, layout, gather), rbd_device_us (upload, launches, statuses back). */
@@ -821,6 +824,91 @@ typedef struct kd_leaves {
  * are expanded breadth-first, then subtrees are walked depth-first by `threads` (0 = up to 16). */
 int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* subpath, int cmp0, int cmp1,
             int threads, kd_leaves** out);
+
+/* -------- device leaf join: changed leaf trees parsed, joined and pruned on the GPU -------- */
+/* The lowest level of a pruned walk: at a high edit rate every leaf tree of both sides has changed and
+ * each one is parsed and joined entry by entry.  The decoder (kart_amd/csrc/kd_treeparse.h, written
+ * from git's tree format: <octal mode> SP <name> NUL <20 OID bytes>, repeated) defines the device class
+ * of a tree — stricter than the host walk's parser, never laxer.  Status of one task (the status of the
+ * first of its roots' trees that is refused): */
+#define KD_TJ_OK 0u
+#define KD_TJ_EMODE 1u   /* a mode byte that is no octal digit, no digits, more than 11 digits or a value
+                            above 2^32 - 1, or the tree ends inside a mode                              */
+#define KD_TJ_ENAME 2u   /* an empty name, or no NUL before the end of the tree                         */
+#define KD_TJ_EOID 3u    /* fewer than 20 bytes behind a name's NUL                                      */
+#define KD_TJ_ETREE 4u   /* an entry of mode 040000 (a subtree at leaf depth is the host walk's)         */
+#define KD_TJ_EORDER 5u  /* a name not strictly above the one before it (unsigned bytes, then length)    */
+#define KD_TJ_EBIG 6u    /* a tree above KD_TJ_MAX_BYTES, or a task whose kept paths of one root pass
+                            2^32 - 1 bytes                                                               */
+#define KD_TJ_ECAP 7u    /* mem = KD_MEM_DEVICE only: the task's output ranges pass cap_n / cap_bytes     */
+#define KD_TJ_ERANGE 11u /* tree[] names no tree of the arena; offsets that descend or pass their end    */
+#define KD_TJ_MAX_BYTES (1u << 30) /* the largest tree the join takes                                    */
+/* One root's output of kd_tree_join_batch, in kd_leaves layout.  The caller owns the arrays: path_off
+ * [cap_n + 1], mode [cap_n], oid [20 * cap_n], path [cap_bytes].  n and bytes are results (host words
+ * with mem = KD_MEM_HOST; with KD_MEM_DEVICE they are written to totals, see below). */
+typedef struct kd_tj_out {
+    uint64_t cap_n, cap_bytes;
+    uint64_t* path_off;
+    uint32_t* mode;
+    uint8_t* oid;
+    uint8_t* path;
+    uint64_t n, bytes;
+} kd_tj_out;
+/* n_task tasks over an arena of inflated tree objects: tree i = data[off[i] .. off[i+1]) (off [n_trees +
+ * 1], 64-bit, a tree may start at any byte; trees are read 8 bytes at a time at byte addresses, so with
+ * mem = KD_MEM_DEVICE data must be readable up to off[n_trees] + 8 bytes; what lies there is never used).  Task t names up to k <= 3 trees, one per root: tree[t*k + r], or KD_NONE where root r
+ * has no tree at this path, and a path prefix pfx[pfx_off[t] .. pfx_off[t+1]).  The k entry lists are
+ * merged by name exactly as kd_walk joins a level (Walk::join + Walk::pruned restricted to non-tree
+ * entries): a name is dropped in every root when roots cmp0 and cmp1 agree on it (both lack it, or both
+ * have it with equal mode and OID; KD_WALK_ALL for both: nothing is dropped), every other entry is kept
+ * in each root that has it.  out[r] receives root r's kept entries in task order and name order:
+ * path = prefix + '/' + name (no '/' after an empty prefix), path_off (path_off[0] = 0), mode, oid;
+ * count[t*k + r] the entries task t kept in root r; status[t] = KD_TJ_*.  A task with a nonzero status
+ * contributes nothing and nothing of it is written (its counts are 0).
+ * Three steps: k_tj_count (one lane per task: every tree validated, then the join counted), the
+ * project's k_gf_scan over the counts, k_tj_emit (the same join again, writing at the scanned
+ * positions): positions are deterministic, no atomic decides one.  All kept entries and path bytes of one
+ * call, over all roots together, must stay below 2^32 (the scan is 32-bit): kd_walk_device-style callers
+ * batch far below that.
+ * mem = KD_MEM_HOST: every array is host memory, staged by the library; offsets are checked (descending:
+ * KD_EINVAL), totals above a root's cap_n / cap_bytes are KD_EINVAL with nothing written, and the call
+ * returns with the results.  totals is ignored.
+ * mem = KD_MEM_DEVICE: every array (out[r]'s arrays too; out itself is host memory) is device memory and
+ * the call is queued on the context's stream; totals [2*k] (device) <- (n, bytes) per root; a task whose
+ * ranges pass a cap gets KD_TJ_ECAP and writes nothing. */
+int kd_tree_join_batch(kd_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n_trees, const uint32_t* tree,
+                       const uint8_t* pfx, const uint64_t* pfx_off, uint64_t n_task, int k, int cmp0, int cmp1,
+                       kd_tj_out* out, uint32_t* count, uint8_t* status, uint64_t* totals, uint32_t mem);
+
+/* kd_walk with its lowest level on the GPU (an opt-in route): out[0..k) is what kd_walk returns for the
+ * same roots, subpath and compare roots, byte for byte (n, path_off, mode, oid, path, present), and a
+ * missing or corrupt tree gives the code kd_walk gives.  The host peels the roots, follows `subpath` and
+ * expands `depth` levels below the walked tree breadth-first, in parallel, with pruning (depth = the number
+ * of path components above the trees handed over; 0 hands over the walked tree itself; Kart passes its
+ * path encoding's levels).  A blob met above `depth` is emitted by the host; every subtree item left at
+ * `depth` is a task.  Tasks go in batches of about walk_batch_bytes (each tree counted as the compressed
+ * span the device read ships for it: its entry's size + size/4096 + size/16384 + size/2^25 + 13; 4 KiB for
+ * a loose tree): a batch's tree ids are made unique, read through the batched device read with trees as
+ * the expected type (flags: KD_RBD_DELTAS rebuilds delta-compressed trees on the device too) and joined
+ * by kd_tree_join_batch in HBM.  A task is host class — walked by kd_walk's own code, with the same
+ * result — when one of its trees is above KD_INF_MAX, is missing or corrupt, or gets a KD_TJ_* status
+ * (a subtree at that depth, names out of order, ...).
+ * A delta-compressed tree is counted by its delta's size (the tree's is known only after the read's plan): on
+ * a repacked repository a batch's arena and outputs can be several times walk_batch_bytes, and where a
+ * batch's join could keep 2^31 entries and path bytes the rest of that batch's tasks are host class (seen
+ * in stats[2] only).  The trees' costs are taken by every thread (a locate and an entry header per tree); a
+ * batch's ids are sorted and made unique on one: stats[11].
+ * stats [KD_WD_STATS] (may be NULL): [0] tasks, [1] tasks joined on the device, [2] host-class tasks
+ * ([1] + [2] == [0]), [3] unique trees requested (summed over batches), [4] trees inflated on the device,
+ * [5] trees read on the host, [6] fixups, [7] compressed bytes uploaded, [8] trees rebuilt from a delta
+ * chain on the device, [9] batches; microseconds of [10] the host expansion, [11] forming the batches,
+ * the reads' [12] locate / plan, [13] host reads and gather, [14] upload, inflate / delta kernels and
+ * statuses back, the join's [15] task lists, allocations and upload, [16] kernels (to the counts' arrival),
+ * [17] downloads (offsets, results) and frees, [18] stitching, [19] host-class walks, [20] the whole call (what [10..19] leave of
+ * it: per-batch vectors built and freed, device allocations and frees between the timed spans); [21..23] 0. */
+#define KD_WD_STATS 24
+int kd_walk_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* roots, int k, const char* subpath, int cmp0, int cmp1,
+                   int threads, int depth, uint32_t flags, kd_leaves** out, uint64_t* stats);
 
 /* -------- profiling (hipEvents around every launch on the context stream) -------- */
 int kd_prof_enable(kd_ctx* ctx, int on);

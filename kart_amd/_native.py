@@ -45,6 +45,11 @@ KD_INF_MAX = 256 << 10  # the largest blob kd_odb_read_batch_device inflates on 
 KD_DL_ERANGE = 11
 KD_DL_MAX_DEPTH = 64  # the deepest chain kd_odb_read_batch_device_ex rebuilds on the device
 KD_RBD_DELTAS = 1     # kd_odb_read_batch_device_ex flag: delta chains rebuilt on the device
+# kd_tree_join_batch's status of one task (kartdiff.h KD_TJ_*)
+(KD_TJ_OK, KD_TJ_EMODE, KD_TJ_ENAME, KD_TJ_EOID, KD_TJ_ETREE, KD_TJ_EORDER, KD_TJ_EBIG, KD_TJ_ECAP) = range(8)
+KD_TJ_ERANGE = 11
+KD_TJ_MAX_BYTES = 1 << 30  # the largest tree the join takes
+KD_WD_STATS = 24           # kd_walk_device's counters
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -80,6 +85,20 @@ class KdLeaves(ctypes.Structure):
         ("oid", c_u8p),
         ("path", c_u8p),
         ("present", ctypes.c_int32),
+    ]
+
+
+class KdTjOut(ctypes.Structure):
+    """kd_tj_out (kd_tree_join_batch): one root's kept entries in kd_leaves layout, caller-owned arrays"""
+    _fields_ = [
+        ("cap_n", ctypes.c_uint64),
+        ("cap_bytes", ctypes.c_uint64),
+        ("path_off", ctypes.c_void_p),
+        ("mode", ctypes.c_void_p),
+        ("oid", ctypes.c_void_p),
+        ("path", ctypes.c_void_p),
+        ("n", ctypes.c_uint64),
+        ("bytes", ctypes.c_uint64),
     ]
 
 
@@ -419,6 +438,17 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
          ctypes.POINTER(ctypes.POINTER(KdLeaves))],
+    ),
+    "kd_walk_device": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+         ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(KdLeaves)), c_u64p],
+    ),
+    "kd_tree_join_batch": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KdTjOut),
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32],
     ),
     "kd_prof_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "kd_prof_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),

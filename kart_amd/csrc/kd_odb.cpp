@@ -149,6 +149,9 @@ struct kd_odb {
     std::vector<Reader*> pool;
     // options (kd_odb_set_option; kd_odb_open seeds them from the environment)
     int zlib_only = 0;  // "zlib" [KD_ODB_ZLIB]: 1 = inflate with zlib even when libdeflate is present (A/B)
+    // "walk_batch_bytes" [KD_WALK_BATCH_BYTES]: kd_walk_device reads its leaf trees in batches of about this
+    // many compressed and host-read bytes (what bounds the pinned staging and the device arena of a walk)
+    u64 walk_batch_bytes = 64ull << 20;
     // kd_odb_read_batch_device: the pinned staging its sources are gathered into (grow-only), one call at a time
     std::mutex dev_mu;
     u8* pin = nullptr;
@@ -835,6 +838,10 @@ extern "C" int kd_odb_open(const char* gitdir, kd_odb** out) {
     }
     kd_odb* db = new kd_odb();
     if (const char* v = std::getenv("KD_ODB_ZLIB")) db->zlib_only = (int)strtol(v, nullptr, 10) != 0;
+    if (const char* v = std::getenv("KD_WALK_BATCH_BYTES")) {
+        const long long b = strtoll(v, nullptr, 10);
+        if (b > 0) db->walk_batch_bytes = (u64)b;
+    }
     add_objdir(db, dir + "/objects", 0);
     *out = db;
     return KD_OK;
@@ -842,6 +849,12 @@ extern "C" int kd_odb_open(const char* gitdir, kd_odb** out) {
 
 extern "C" int kd_odb_set_option(kd_odb* odb, const char* name, int64_t value) {
     if (!odb || !name) { kd::set_error("kd_odb_set_option: NULL"); return KD_EINVAL; }
+    if (strcmp(name, "walk_batch_bytes") == 0) {
+        if (value <= 0) { kd::set_error("kd_odb_set_option: walk_batch_bytes must be positive"); return KD_EINVAL; }
+        std::lock_guard<std::mutex> lk(odb->dev_mu);
+        odb->walk_batch_bytes = (u64)value;
+        return KD_OK;
+    }
     if (strcmp(name, "zlib") != 0) { kd::set_error("kd_odb_set_option: unknown option '%s'", name); return KD_EINVAL; }
     std::lock_guard<std::mutex> lk(odb->pool_mu);
     odb->zlib_only = value != 0;
@@ -859,6 +872,11 @@ extern "C" int kd_odb_get_option(kd_odb* odb, const char* name, int64_t* value) 
             *value = odb->rbd_us[k];
             return KD_OK;
         }
+    if (strcmp(name, "walk_batch_bytes") == 0) {
+        std::lock_guard<std::mutex> lk(odb->dev_mu);
+        *value = (int64_t)odb->walk_batch_bytes;
+        return KD_OK;
+    }
     if (strcmp(name, "zlib") != 0) { kd::set_error("kd_odb_get_option: unknown option '%s'", name); return KD_EINVAL; }
     *value = odb->zlib_only;
     return KD_OK;
@@ -1040,8 +1058,11 @@ u32 find_node(const std::vector<DlNode>& nodes, u64 key) {
     return it != nodes.end() && it->key == key ? (u32)(it - nodes.begin()) : ~0u;
 }
 
+// want_type: the object type the ids must name (OBJ_BLOB for the public entry points, OBJ_TREE for kd_walk_device's
+// leaf trees); status 2 for anything else
 int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64_t n, int threads, uint32_t flags, kd_blobs* out,
-                           uint8_t* status, uint64_t st8[8]) {
+                           uint8_t* status, uint64_t st8[8], int want_type = OBJ_BLOB,
+                           int64_t* phase_us = nullptr) {
     const bool deltas = (flags & KD_RBD_DELTAS) != 0;
     const auto t_start = Clock::now();
     out->n = n;
@@ -1089,7 +1110,7 @@ int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64
                 if (!pk.find(boid, &cur)) nd.bad = 1;  // the base is in another pack, loose, or nowhere
             } else {
                 nd.rsize = sz;
-                nd.bad = t != OBJ_BLOB;
+                nd.bad = t != want_type;
                 recs[tid].push_back(nd);
                 return;
             }
@@ -1111,7 +1132,7 @@ int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64
             const u8* boid = nullptr;
             const Pack& pk = *odb->packs[p];
             if (rd.entry_header(pk, o, &type, &size, &data, &boff, &boid) != RD_OK) continue;
-            if (type == OBJ_BLOB && size <= KD_INF_MAX && data < pk.pack.n - 20) {
+            if (type == want_type && size <= KD_INF_MAX && data < pk.pack.n - 20) {
                 it[i].dev = 1;
                 it[i].data = data;
                 it[i].size = size;
@@ -1237,7 +1258,7 @@ int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64
                 int type = 0;
                 const int rc = key != ~0ull ? rd.read_packed(*odb->packs[key >> 48], key & ((1ull << 48) - 1), &type, buf)
                                             : rd.read(oids + 20 * i, &type, buf);
-                status[i] = rc == RD_OK && type != OBJ_BLOB ? 2 : (u8)rc;
+                status[i] = rc == RD_OK && type != want_type ? 2 : (u8)rc;
                 if (status[i]) buf.clear();
                 at[i] = part[c].size();
                 chunk_of[i] = (u32)c;
@@ -1400,7 +1421,7 @@ int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64
         const auto t_dev = Clock::now();
         // 5: the arena and its offsets in HBM, one upload, one launch (KD_RBD_DELTAS: two, and one per level)
         void *d_data = nullptr, *d_off = nullptr;
-        int rc = kd_malloc(ctx, std::max<u64>(off[n], 16), &d_data);
+        int rc = kd_malloc(ctx, off[n] + 16, &d_data);  // (the tree join reads up to 8 bytes past the last object)
         if (!rc) rc = kd_malloc(ctx, 8 * (n + 1), &d_off);
         if (!rc && !deltas)
             rc = kd::inflate_from_host(ctx, pin, soff.data(), kind.data(), n, (u8*)d_data, off.data(), (u64*)d_off, dstat.data());
@@ -1448,7 +1469,7 @@ int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64
                     if (!forced[i] && it[i].dev == 2) nfixd++;
                     int type = 0;
                     const int hr = rd.read_packed(*odb->packs[it[i].key >> 48], it[i].key & ((1ull << 48) - 1), &type, buf);
-                    if (hr == RD_OK && type == OBJ_BLOB && buf.size() == it[i].size) {
+                    if (hr == RD_OK && type == want_type && buf.size() == it[i].size) {
                         if (it[i].size) {
                             rc = kd_memcpy(ctx, (u8*)d_data + off[i], buf.data(), it[i].size, KD_COPY_H2D);
                             if (!rc) rc = kd_sync(ctx);  // (before buf is read into again; a rare path)
@@ -1484,6 +1505,11 @@ int read_batch_device_impl(kd_ctx* ctx, kd_odb* odb, const uint8_t* oids, uint64
         st8[7] = ws_bytes;
         break;
     }
+    if (phase_us) {  // (kd_walk_device sums its batches' phases)
+        phase_us[0] += plan_us;
+        phase_us[1] += host_us;
+        phase_us[2] += device_us;
+    }
     if (deltas) {
         odb->rbd_us[0] = plan_us;
         odb->rbd_us[1] = peek_us;
@@ -1514,26 +1540,13 @@ extern "C" int kd_odb_read_batch_device_ex(kd_ctx* ctx, kd_odb* odb, const uint8
     return rc;
 }
 
-extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* subpath, int cmp0, int cmp1, int threads,
-                       kd_leaves** out) {
-    if (!odb || !roots || !out || k < 1 || k > KMAX) { kd::set_error("kd_walk: bad arguments"); return KD_EINVAL; }
-    if ((cmp0 < 0) != (cmp1 < 0) || cmp0 >= k || cmp1 >= k || (cmp0 >= 0 && cmp0 == cmp1)) {
-        kd::set_error("kd_walk: compare roots %d/%d of %d", cmp0, cmp1, k);
-        return KD_EINVAL;
-    }
-    for (int r = 0; r < k && r < KMAX; r++) out[r] = nullptr;
-    const int nt = default_threads(threads);
-    Walk W;
-    W.k = k;
-    W.c0 = cmp0 < 0 ? -1 : cmp0;
-    W.c1 = cmp1 < 0 ? -1 : cmp1;
-    Reader rd0(odb);
-    // ---- the walked tree of each root: peel commits, then follow `subpath` ----
-    Item top;
+namespace {
+// the walked tree of each root: peel commits, then follow `subpath`
+int walk_top(kd_odb* odb, Reader& rd0, const uint8_t* roots, int k, const char* subpath, const char* who, Item& top) {
     std::string msg;
     for (int r = 0; r < k && r < KMAX; r++) {
         int rc = peel_to_tree(rd0, roots + 20 * r, top.oid[r], msg);
-        if (rc) { kd::set_error("kd_walk: %s", msg.c_str()); return rc; }
+        if (rc) { kd::set_error("%s: %s", who, msg.c_str()); return rc; }
         top.has[r] = 1;
         top.mode[r] = 040000;
     }
@@ -1554,7 +1567,7 @@ extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* sub
                 if (rc || type != OBJ_TREE || !parse_tree(buf, ents)) {
                     char hx[41];
                     hex40(top.oid[r], hx);
-                    kd::set_error("kd_walk: cannot read tree %s", hx);
+                    kd::set_error("%s: cannot read tree %s", who, hx);
                     return rc == RD_MISSING ? KD_ENOTFOUND : KD_EINVAL;
                 }
                 top.has[r] = 0;
@@ -1568,42 +1581,28 @@ extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* sub
         }
         a = b + 1;
     }
-    // ---- items: the top expanded breadth-first (in parallel) until there is work for every thread ----
-    std::vector<Item> items;
-    if (!W.pruned(top) && std::any_of(top.has, top.has + k, [](u8 h) { return h != 0; })) items.push_back(top);
-    for (int level = 0; level < 4; level++) {
-        size_t ntree = 0;
-        for (auto& it : items) ntree += it.tree;
-        if (ntree == 0 || ntree >= (size_t)nt * 16) break;
-        std::vector<std::vector<Item>> kids(items.size());
-        std::vector<std::unique_ptr<Reader>> rds(nt);
-        par_items(items.size(), nt, [&](size_t i, int tid) {
-            if (!items[i].tree) { kids[i].push_back(items[i]); return; }
-            if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
-            W.expand(*rds[tid], items[i], [&](const Item& c) { kids[i].push_back(c); });
-        });
-        if (W.err) break;
-        std::vector<Item> next;
-        for (auto& v : kids)
-            for (auto& c : v) next.push_back(std::move(c));
-        items.swap(next);
-    }
-    // ---- every item walked by some thread into its own outputs; then stitched in item order ----
-    std::vector<WalkOut> outs;
-    if (!W.err) {
-        outs.resize(items.size() * k);
-        std::vector<std::unique_ptr<Reader>> rds(nt);
-        par_items(items.size(), nt, [&](size_t i, int tid) {
-            WalkOut* o = &outs[i * k];
-            if (!items[i].tree) { W.emit(items[i], o); return; }
-            if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
-            W.walk_item(*rds[tid], items[i], o);
-        });
-    }
-    if (W.err) {
-        kd::set_error("kd_walk: %s", W.emsg.c_str());
-        return W.err.load();
-    }
+    return KD_OK;
+}
+
+// one level of breadth-first expansion, in parallel: every subtree item replaced by its children
+void walk_expand_level(kd_odb* odb, Walk& W, std::vector<Item>& items, int nt) {
+    std::vector<std::vector<Item>> kids(items.size());
+    std::vector<std::unique_ptr<Reader>> rds(nt);
+    par_items(items.size(), nt, [&](size_t i, int tid) {
+        if (!items[i].tree) { kids[i].push_back(items[i]); return; }
+        if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
+        W.expand(*rds[tid], items[i], [&](const Item& c) { kids[i].push_back(c); });
+    });
+    if (W.err) return;
+    std::vector<Item> next;
+    for (auto& v : kids)
+        for (auto& c : v) next.push_back(std::move(c));
+    items.swap(next);
+}
+
+// every item's outputs stitched in item order into one block per root
+int walk_stitch(const std::vector<Item>& items, const std::vector<WalkOut>& outs, int k, const Item& top, int nt, const char* who,
+                kd_leaves** out) {
     for (int r = 0; r < k && r < KMAX; r++) {
         u64 n = 0, bytes = 0;
         for (size_t i = 0; i < items.size(); i++) {
@@ -1615,8 +1614,8 @@ extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* sub
         const size_t total = hsz + 8 * (n + 1) + 4 * n + 20 * n + bytes + 16;
         u8* blk = (u8*)std::malloc(total);
         if (!blk) {
-            for (int q = 0; q < r; q++) std::free(out[q]);
-            kd::set_error("kd_walk: out of memory (%llu leaves)", (unsigned long long)n);
+            for (int q = 0; q < r; q++) { std::free(out[q]); out[q] = nullptr; }
+            kd::set_error("%s: out of memory (%llu leaves)", who, (unsigned long long)n);
             return KD_EINVAL;
         }
         kd_leaves* L = (kd_leaves*)blk;
@@ -1645,4 +1644,345 @@ extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* sub
         out[r] = L;
     }
     return KD_OK;
+}
+}  // namespace
+
+extern "C" int kd_walk(kd_odb* odb, const uint8_t* roots, int k, const char* subpath, int cmp0, int cmp1, int threads,
+                       kd_leaves** out) {
+    if (!odb || !roots || !out || k < 1 || k > KMAX) { kd::set_error("kd_walk: bad arguments"); return KD_EINVAL; }
+    if ((cmp0 < 0) != (cmp1 < 0) || cmp0 >= k || cmp1 >= k || (cmp0 >= 0 && cmp0 == cmp1)) {
+        kd::set_error("kd_walk: compare roots %d/%d of %d", cmp0, cmp1, k);
+        return KD_EINVAL;
+    }
+    for (int r = 0; r < k && r < KMAX; r++) out[r] = nullptr;
+    const int nt = default_threads(threads);
+    Walk W;
+    W.k = k;
+    W.c0 = cmp0 < 0 ? -1 : cmp0;
+    W.c1 = cmp1 < 0 ? -1 : cmp1;
+    Reader rd0(odb);
+    Item top;
+    if (int rc = walk_top(odb, rd0, roots, k, subpath, "kd_walk", top)) return rc;
+    // ---- items: the top expanded breadth-first (in parallel) until there is work for every thread ----
+    std::vector<Item> items;
+    if (!W.pruned(top) && std::any_of(top.has, top.has + k, [](u8 h) { return h != 0; })) items.push_back(top);
+    for (int level = 0; level < 4; level++) {
+        size_t ntree = 0;
+        for (auto& it : items) ntree += it.tree;
+        if (ntree == 0 || ntree >= (size_t)nt * 16) break;
+        walk_expand_level(odb, W, items, nt);
+        if (W.err) break;
+    }
+    // ---- every item walked by some thread into its own outputs; then stitched in item order ----
+    std::vector<WalkOut> outs;
+    if (!W.err) {
+        outs.resize(items.size() * k);
+        std::vector<std::unique_ptr<Reader>> rds(nt);
+        par_items(items.size(), nt, [&](size_t i, int tid) {
+            WalkOut* o = &outs[i * k];
+            if (!items[i].tree) { W.emit(items[i], o); return; }
+            if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
+            W.walk_item(*rds[tid], items[i], o);
+        });
+    }
+    if (W.err) {
+        kd::set_error("kd_walk: %s", W.emsg.c_str());
+        return W.err.load();
+    }
+    return walk_stitch(items, outs, k, top, nt, "kd_walk", out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// kd_walk with its lowest level on the GPU: the host expands `depth` levels, the subtree items left at
+// that depth become tasks of kd_tree_join_batch over trees read by the batched device read
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct OidKey {
+    u8 b[20];
+    bool operator<(const OidKey& o) const { return memcmp(b, o.b, 20) < 0; }
+    bool operator==(const OidKey& o) const { return memcmp(b, o.b, 20) == 0; }
+};
+
+// what a packed or loose tree costs a batch: the compressed span the device read ships for it, or the bytes the
+// host reads for it (the entry header's size either way; 4 KiB where unknown).  For a delta entry the header's
+// size is the delta's, not the tree's (that is known only after the plan's peek): on a repacked repository a
+// batch's arena and outputs can be several times walk_batch_bytes (kartdiff.h says so)
+u64 tree_cost(kd_odb* odb, Reader& rd, const u8* oid) {
+    u64 o;
+    const long p = rd.locate(oid, &o);
+    int type;
+    u64 size, data, boff = 0;
+    const u8* boid = nullptr;
+    if (p < 0 || rd.entry_header(*odb->packs[p], o, &type, &size, &data, &boff, &boid) != RD_OK) return 4096;
+    return inf_bound(size);
+}
+}  // namespace
+
+extern "C" int kd_walk_device(kd_ctx* ctx, kd_odb* odb, const uint8_t* roots, int k, const char* subpath, int cmp0, int cmp1,
+                              int threads, int depth, uint32_t flags, kd_leaves** out, uint64_t* stats) {
+    if (!ctx || !odb || !roots || !out || k < 1 || k > KMAX || depth < 0 || depth > 64) {
+        kd::set_error("kd_walk_device: bad arguments");
+        return KD_EINVAL;
+    }
+    if ((cmp0 < 0) != (cmp1 < 0) || cmp0 >= k || cmp1 >= k || (cmp0 >= 0 && cmp0 == cmp1)) {
+        kd::set_error("kd_walk_device: compare roots %d/%d of %d", cmp0, cmp1, k);
+        return KD_EINVAL;
+    }
+    if (flags & ~KD_RBD_DELTAS) { kd::set_error("kd_walk_device: unknown flags %u", flags); return KD_EINVAL; }
+    for (int r = 0; r < k; r++) out[r] = nullptr;
+    u64 st[KD_WD_STATS];
+    memset(st, 0, sizeof st);
+    const int nt = default_threads(threads);
+    Walk W;
+    W.k = k;
+    W.c0 = cmp0 < 0 ? -1 : cmp0;
+    W.c1 = cmp1 < 0 ? -1 : cmp1;
+    Reader rd0(odb);
+    Item top;
+    const auto t_call = Clock::now();
+    auto t0 = Clock::now();
+    if (int rc = walk_top(odb, rd0, roots, k, subpath, "kd_walk_device", top)) return rc;
+    // ---- host expansion: `depth` levels below the walked tree, breadth-first, pruned ----
+    std::vector<Item> items;
+    if (!W.pruned(top) && std::any_of(top.has, top.has + k, [](u8 h) { return h != 0; })) items.push_back(top);
+    for (int level = 0; level < depth && !W.err; level++) {
+        if (std::none_of(items.begin(), items.end(), [](const Item& it) { return it.tree; })) break;
+        walk_expand_level(odb, W, items, nt);
+    }
+    if (W.err) {
+        kd::set_error("kd_walk_device: %s", W.emsg.c_str());
+        return W.err.load();
+    }
+    st[10] = (u64)us_since(t0);
+    // ---- tasks: every subtree item left; a blob item is the host's, emitted as kd_walk emits it ----
+    std::vector<WalkOut> outs(items.size() * k);
+    std::vector<size_t> task_item;
+    for (size_t i = 0; i < items.size(); i++) {
+        if (items[i].tree) task_item.push_back(i);
+        else W.emit(items[i], &outs[i * k]);
+    }
+    const u64 ntask = task_item.size();
+    st[0] = ntask;
+    std::vector<u8> on_host(ntask, 0);
+    u64 batch_bytes;
+    {
+        std::lock_guard<std::mutex> lk(odb->dev_mu);
+        batch_bytes = odb->walk_batch_bytes;
+    }
+    int rc = KD_OK;
+    int64_t read_us[3] = {0, 0, 0};  // the batched reads' plan, host reads + gather, device
+    // what each task costs a batch, by every thread (a locate and an entry header per tree)
+    t0 = Clock::now();
+    std::vector<u64> task_cost(ntask, 0);
+    {
+        constexpr u64 CH = 256;
+        std::vector<std::unique_ptr<Reader>> rds(nt);
+        par_items((ntask + CH - 1) / CH, nt, [&](size_t c, int tid) {
+            if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
+            for (u64 t = c * CH; t < std::min(ntask, (c + 1) * CH); t++) {
+                const Item& it = items[task_item[t]];
+                for (int r = 0; r < k; r++)
+                    if (it.has[r]) task_cost[t] += tree_cost(odb, *rds[tid], it.oid[r]);
+            }
+        });
+    }
+    st[11] += (u64)us_since(t0);
+    for (u64 lo = 0; lo < ntask && !rc;) {
+        // ---- one batch: tasks [lo, hi), their trees made unique ----
+        t0 = Clock::now();
+        std::vector<OidKey> uniq;
+        u64 hi = lo, cost = 0;
+        for (; hi < ntask; hi++) {
+            const Item& it = items[task_item[hi]];
+            const u64 c = task_cost[hi];
+            if (hi > lo && cost + c > batch_bytes) break;
+            cost += c;
+            for (int r = 0; r < k; r++)
+                if (it.has[r]) {
+                    OidKey q;
+                    memcpy(q.b, it.oid[r], 20);
+                    uniq.push_back(q);
+                }
+        }
+        std::sort(uniq.begin(), uniq.end());
+        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+        const u64 nu = uniq.size();
+        st[3] += nu;
+        st[9]++;
+        st[11] += (u64)us_since(t0);
+        t0 = Clock::now();
+        // ---- the trees read through the batched device read (expected type: tree) ----
+        std::vector<u8> rstat(std::max<u64>(nu, 1), 0);
+        const int64_t read_before = read_us[0] + read_us[1] + read_us[2];
+        kd_blobs arena{};
+        u64 st8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        rc = read_batch_device_impl(ctx, odb, (const u8*)uniq.data(), nu, threads, flags, &arena, rstat.data(), st8, OBJ_TREE, read_us);
+        if (rc) break;
+        st[4] += st8[0];
+        st[5] += st8[1];
+        st[6] += st8[3];
+        st[7] += st8[2];
+        st[8] += st8[4];
+        std::vector<u64> off(nu + 1);
+        rc = kd_memcpy(ctx, off.data(), arena.off, 8 * (nu + 1), KD_COPY_D2H);
+        if (!rc) rc = kd_sync(ctx);
+        st[17] += (u64)std::max<int64_t>(0, us_since(t0) - ((read_us[0] + read_us[1] + read_us[2]) - read_before));  // (the offsets back)
+        t0 = Clock::now();
+        // ---- device tasks: every tree read, none above KD_INF_MAX; the join's own bound on a call ----
+        std::vector<u32> tix;         // [nd * k]
+        std::vector<u64> dtask;       // the batch's device tasks (indices into task_item)
+        std::vector<u64> poff{0};
+        std::string pfx;
+        u64 cap_n[KMAX] = {0, 0, 0}, cap_b[KMAX] = {0, 0, 0}, bound = 0;
+        for (u64 t = lo; t < hi && !rc; t++) {
+            const Item& it = items[task_item[t]];
+            u32 ix[KMAX] = {KD_NONE, KD_NONE, KD_NONE};
+            bool dev = true;
+            u64 tb = 0;
+            for (int r = 0; r < k; r++) {
+                if (!it.has[r]) continue;
+                OidKey q;
+                memcpy(q.b, it.oid[r], 20);
+                const u64 u = (u64)(std::lower_bound(uniq.begin(), uniq.end(), q) - uniq.begin());
+                const u64 L = off[u + 1] - off[u];
+                if (rstat[u] != 0 || L > KD_INF_MAX) dev = false;
+                ix[r] = (u32)u;
+                tb += L + (L / 23) * (it.path.size() + 2);
+            }
+            if (!dev || bound + tb >= (1ull << 31)) {  // (a batch that large: the rest of it is the host's)
+                on_host[t] = 1;
+                continue;
+            }
+            bound += tb;
+            for (int r = 0; r < k; r++) {
+                tix.push_back(ix[r]);
+                if (ix[r] == KD_NONE) continue;
+                const u64 L = off[ix[r] + 1] - off[ix[r]];
+                cap_n[r] += L / 23;
+                cap_b[r] += L + (L / 23) * (it.path.size() + 1);
+            }
+            dtask.push_back(t);
+            pfx += it.path;
+            poff.push_back(pfx.size());
+        }
+        const u64 nd = dtask.size();
+        // ---- the join on the device, its results back ----
+        std::vector<u32> cnt(std::max<u64>(nd * k, 1), 0);
+        std::vector<u8> jst(std::max<u64>(nd, 1), 0);
+        std::vector<u64> tot(2 * KMAX, 0);
+        std::vector<std::vector<u8>> hpath(k), hoid(k);
+        std::vector<std::vector<u64>> hpoff(k);
+        std::vector<std::vector<u32>> hmode(k);
+        if (!rc && nd) {
+            std::vector<void*> dev;
+            auto dalloc = [&](u64 bytes, const void* src) -> void* {
+                void* p = nullptr;
+                if (rc) return p;
+                rc = kd_malloc(ctx, std::max<u64>(bytes, 16), &p);
+                if (!rc) dev.push_back(p);
+                if (!rc && src && bytes) rc = kd_memcpy(ctx, p, src, bytes, KD_COPY_H2D);
+                return p;
+            };
+            void* d_tix = dalloc(4 * nd * k, tix.data());
+            void* d_pfx = dalloc(pfx.size(), pfx.data());
+            void* d_poff = dalloc(8 * (nd + 1), poff.data());
+            void* d_cnt = dalloc(4 * nd * k, nullptr);
+            void* d_st = dalloc(nd, nullptr);
+            void* d_tot = dalloc(16 * KMAX, nullptr);
+            kd_tj_out jo[KMAX];
+            memset(jo, 0, sizeof jo);
+            for (int r = 0; r < k; r++) {
+                jo[r].cap_n = cap_n[r];
+                jo[r].cap_bytes = cap_b[r];
+                jo[r].path_off = (uint64_t*)dalloc(8 * (cap_n[r] + 1), nullptr);
+                jo[r].mode = (uint32_t*)dalloc(4 * cap_n[r], nullptr);
+                jo[r].oid = (uint8_t*)dalloc(20 * cap_n[r], nullptr);
+                jo[r].path = (uint8_t*)dalloc(cap_b[r], nullptr);
+            }
+            if (!rc) rc = kd_sync(ctx);  // (the uploads read pageable vectors)
+            st[15] += (u64)us_since(t0);
+            t0 = Clock::now();
+            if (!rc)
+                rc = kd_tree_join_batch(ctx, arena.data, arena.off, nu, (const u32*)d_tix, (const u8*)d_pfx, (const u64*)d_poff, nd, k,
+                                        cmp0, cmp1, jo, (u32*)d_cnt, (u8*)d_st, (u64*)d_tot, KD_MEM_DEVICE);
+            if (!rc) rc = kd_memcpy(ctx, tot.data(), d_tot, 16 * k, KD_COPY_D2H);
+            if (!rc) rc = kd_memcpy(ctx, cnt.data(), d_cnt, 4 * nd * k, KD_COPY_D2H);
+            if (!rc) rc = kd_memcpy(ctx, jst.data(), d_st, nd, KD_COPY_D2H);
+            if (!rc) rc = kd_sync(ctx);
+            st[16] += (u64)us_since(t0);  // (the kernels and three small copies behind them)
+            t0 = Clock::now();
+            for (int r = 0; r < k && !rc; r++) {
+                const u64 n = tot[2 * r], nbytes = tot[2 * r + 1];
+                if (n > cap_n[r] || nbytes > cap_b[r]) {  // (the capacities are upper bounds)
+                    kd::set_error("kd_walk_device: the join kept more than its trees hold");
+                    rc = KD_EINVAL;
+                    break;
+                }
+                hpoff[r].resize(n + 1);
+                hmode[r].resize(n);
+                hoid[r].resize(20 * n);
+                hpath[r].resize(nbytes);
+                rc = kd_memcpy(ctx, hpoff[r].data(), jo[r].path_off, 8 * (n + 1), KD_COPY_D2H);
+                if (!rc && n) rc = kd_memcpy(ctx, hmode[r].data(), jo[r].mode, 4 * n, KD_COPY_D2H);
+                if (!rc && n) rc = kd_memcpy(ctx, hoid[r].data(), jo[r].oid, 20 * n, KD_COPY_D2H);
+                if (!rc && nbytes) rc = kd_memcpy(ctx, hpath[r].data(), jo[r].path, nbytes, KD_COPY_D2H);
+            }
+            if (!rc) rc = kd_sync(ctx);
+            else kd_sync(ctx);
+            for (void* p : dev) kd_mfree(ctx, p);
+        }
+        kd_mfree(ctx, (void*)arena.data);
+        kd_mfree(ctx, (void*)arena.off);
+        st[17] += (u64)us_since(t0);
+        if (rc) break;
+        // ---- a device task's entries into its item's outputs (a refused task is the host's) ----
+        t0 = Clock::now();
+        for (int r = 0; r < k; r++) {
+            std::vector<u64> first(nd + 1, 0);
+            for (u64 j = 0; j < nd; j++) first[j + 1] = first[j] + cnt[j * k + r];
+            par_items(nd, nt, [&](size_t j, int) {
+                if (jst[j] != KD_TJ_OK || !cnt[j * k + r]) return;
+                WalkOut& o = outs[task_item[dtask[j]] * k + r];
+                const u64 e0 = first[j], e1 = first[j + 1], b0 = hpoff[r][e0];
+                o.path.assign((const char*)hpath[r].data() + b0, hpoff[r][e1] - b0);
+                o.end.resize(e1 - e0);
+                for (u64 e = e0; e < e1; e++) o.end[e - e0] = hpoff[r][e + 1] - b0;
+                o.oid.assign(hoid[r].begin() + 20 * e0, hoid[r].begin() + 20 * e1);
+                o.mode.assign(hmode[r].begin() + e0, hmode[r].begin() + e1);
+            });
+        }
+        for (u64 j = 0; j < nd; j++)
+            if (jst[j] != KD_TJ_OK) on_host[dtask[j]] = 1;
+        st[18] += (u64)us_since(t0);
+        lo = hi;
+    }
+    if (rc) return rc;
+    // ---- host-class tasks: the existing walk of the item ----
+    t0 = Clock::now();
+    std::vector<size_t> hostq;
+    for (u64 t = 0; t < ntask; t++)
+        if (on_host[t]) hostq.push_back(task_item[t]);
+    st[2] = hostq.size();
+    st[1] = ntask - hostq.size();
+    {
+        std::vector<std::unique_ptr<Reader>> rds(nt);
+        par_items(hostq.size(), nt, [&](size_t q, int tid) {
+            if (!rds[tid]) rds[tid] = std::make_unique<Reader>(odb);
+            W.walk_item(*rds[tid], items[hostq[q]], &outs[hostq[q] * k]);
+        });
+    }
+    st[19] = (u64)us_since(t0);
+    if (W.err) {
+        kd::set_error("kd_walk_device: %s", W.emsg.c_str());
+        return W.err.load();
+    }
+    t0 = Clock::now();
+    rc = walk_stitch(items, outs, k, top, nt, "kd_walk_device", out);
+    st[18] += (u64)us_since(t0);
+    st[12] = (u64)read_us[0];
+    st[13] = (u64)read_us[1];
+    st[14] = (u64)read_us[2];
+    st[20] = (u64)us_since(t_call);  // the whole call: what [10..19] leave of it is vectors built and freed, allocations
+    if (!rc && stats) memcpy(stats, st, sizeof st);
+    return rc;
 }

@@ -55,6 +55,10 @@ DEVICE_INFLATE = os.environ.get("KD_DEVICE_INFLATE", "0") not in ("", "0")
 # rebuilt on the GPU from their chains instead of read on the host and uploaded.  Off unless
 # KD_DEVICE_DELTAS says otherwise.
 DEVICE_DELTAS = os.environ.get("KD_DEVICE_DELTAS", "0") not in ("", "0")
+# GitRepo.dataset_versions' pruned walk: True = the changed leaf trees are read, parsed, joined and pruned
+# on the GPU (ObjectDB.walk_device) when an engine is passed.  Off unless KD_DEVICE_WALK says otherwise
+# (DESIGN.md §3.7c); on that route delta-compressed trees follow DEVICE_DELTAS.
+DEVICE_WALK = os.environ.get("KD_DEVICE_WALK", "0") not in ("", "0")
 
 
 class Geometry(bytes):

@@ -403,6 +403,52 @@ class Engine:
                 "kd_delta_apply_batch")
         return data[:int(dst_off[-1])], status[:n]
 
+    def tree_join(self, data, off, tree, pfx, pfx_off, k, compare=None):
+        """changed leaf trees parsed, joined and pruned on the GPU (kd_tree_join_batch, host form): tree i
+        is data[off[i]:off[i+1]], task t names tree[t, r] (or KD_NONE) for each of the k roots and the path
+        prefix pfx[pfx_off[t]:pfx_off[t+1]]; ``compare=(i, j)`` drops every name roots i and j agree on.
+        Returns ([(paths uint8, path_off uint64 [n+1], oids uint8 [n, 20], modes uint32 [n]) per root],
+        count uint32 [n_task, k], status uint8 [n_task] of KD_TJ_* codes): what kd_walk lists under those
+        trees; a task with a nonzero status contributes nothing."""
+        data = np.ascontiguousarray(data, np.uint8)
+        pfx = np.ascontiguousarray(pfx, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        pfx_off = np.ascontiguousarray(pfx_off, np.uint64)
+        tree = np.ascontiguousarray(tree, np.uint32).reshape(-1, k)
+        nt, ntrees = int(tree.shape[0]), int(off.shape[0]) - 1
+        if ntrees < 0 or pfx_off.shape[0] != nt + 1:
+            raise ValueError("tree_join: off must hold n_trees + 1 offsets, pfx_off n_task + 1")
+        if int(off[-1]) > data.size or int(pfx_off[-1]) > pfx.size:
+            raise ValueError("tree_join: offsets run past their arena")
+        c0, c1 = compare if compare is not None else (N.KD_WALK_ALL, N.KD_WALK_ALL)
+        # what a root can keep at most: every entry of its trees (23 bytes at least), each under its prefix
+        lens = np.diff(off).astype(np.int64)
+        lead = np.diff(pfx_off).astype(np.int64) + 1
+        outs, arrays = (N.KdTjOut * k)(), []
+        for r in range(k):
+            idx = tree[:, r].astype(np.int64)
+            ok = (idx != N.KD_NONE) & (idx < ntrees)
+            ln = np.where(ok, lens[np.where(ok, idx, 0)] if ntrees else 0, 0)
+            cap_n = int((ln // 23).sum())
+            cap_b = int((ln + (ln // 23) * lead).sum())
+            a = (np.zeros(cap_n + 1, np.uint64), np.zeros(max(cap_n, 1), np.uint32), np.zeros((max(cap_n, 1), 20), np.uint8),
+                 np.zeros(max(cap_b, 1), np.uint8))
+            arrays.append(a)
+            outs[r].cap_n, outs[r].cap_bytes = cap_n, cap_b
+            outs[r].path_off, outs[r].mode, outs[r].oid, outs[r].path = (x.ctypes.data for x in a)
+        count = np.zeros((max(nt, 1), k), np.uint32)
+        status = np.zeros(max(nt, 1), np.uint8)
+        N.check(self.L.kd_tree_join_batch(self.ctx, N.ptr(data) if data.size else N.ptr(_PAD), N.ptr(off), ntrees,
+                                          N.ptr(tree) if nt else N.ptr(_PAD), N.ptr(pfx) if pfx.size else N.ptr(_PAD),
+                                          N.ptr(pfx_off), nt, k, c0, c1, outs, N.ptr(count), N.ptr(status), None,
+                                          N.KD_MEM_HOST), "kd_tree_join_batch")
+        res = []
+        for r in range(k):
+            n, nb = int(outs[r].n), int(outs[r].bytes)
+            po, mo, oo, pa = arrays[r]
+            res.append((pa[:nb], po[:n + 1], oo[:n], mo[:n]))
+        return res, count[:nt], status[:nt]
+
     def merge3(self, ancestor, ours, theirs, flags=0) -> Merge3Result:
         """three PackedSides -> conflicts / merge deltas in path order (kd_merge3; sides packed on the
         GPU with walk-order rows through kd_merge3_device_perm)"""

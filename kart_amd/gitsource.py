@@ -37,6 +37,7 @@ class GitRepo:
         # Kart's index carries a "kart" extension stock git rejects; never touch it
         self.env["GIT_INDEX_FILE"] = index_file or os.path.join(gitdir, "kart_amd.index")
         self.odb = ObjectDB(gitdir)
+        self.last_walk_stats = None  # ObjectDB.walk_device's counters of the last walk on the GPU
         self._promisor = None
 
     def git(self, *args):
@@ -152,15 +153,24 @@ class GitRepo:
             oid = self.rev_tree(oid)
         return self.odb.tree_entries(oid)
 
-    def walk(self, specs, subpath, compare=None):
-        """leaves under ``subpath`` of each revision (odb.Leaves), optionally pruned by ``compare``"""
+    def walk(self, specs, subpath, compare=None, engine=None, depth=None, deltas=False):
+        """leaves under ``subpath`` of each revision (odb.Leaves), optionally pruned by ``compare``.
+        With an ``engine`` and a ``depth`` the trees ``depth`` levels down are read and joined on the GPU
+        (ObjectDB.walk_device: the same leaves; its counters are kept in ``last_walk_stats``)"""
         roots = [self.rev_parse(s) for s in specs]
+
+        def once():
+            if engine is None or depth is None:
+                return self.odb.walk(roots, subpath, compare)
+            leaves, self.last_walk_stats = self.odb.walk_device(engine, roots, subpath, compare, depth=depth, deltas=deltas)
+            return leaves
+
         try:
-            return self.odb.walk(roots, subpath, compare)
+            return once()
         except N.NotFound:
             if not self.odb.refresh():
                 raise
-            return self.odb.walk(roots, subpath, compare)
+            return once()
 
     def ls_tree_r(self, treeish, prefix):
         """[(path, oid hex)] of every blob under ``prefix`` (full paths)"""
@@ -281,27 +291,39 @@ class GitRepo:
         v.partial = partial
         return v
 
-    def dataset_versions(self, specs, ds_path, compare=None):
+    def dataset_versions(self, specs, ds_path, compare=None, engine=None, device_walk=None):
         """DatasetVersion (or None when absent) of ``ds_path`` at each revision, the feature leaves
         from one walk.  ``compare=(i, j)``: prune to the subtrees where revisions i and j differ —
         the versions then hold only those leaves (``.partial``), which is all a diff or merge
-        classification of them needs: every leaf outside is identical on the compared sides."""
+        classification of them needs: every leaf outside is identical on the compared sides.
+        ``device_walk`` (None: ``dataset.DEVICE_WALK``) with an ``engine``: the pruned walk's leaf trees
+        are read and joined on the GPU, ``levels`` of the compared sides' shared path structure down
+        (delta-compressed trees as ``dataset.DEVICE_DELTAS`` says); the versions are the same."""
+        from . import dataset as D
+
         metas = [self._meta(s, ds_path) for s in specs]
         prune = compare is not None and all(metas[i] is not None for i in compare)
         if prune:
             prune = metas[compare[0]][3] == metas[compare[1]][3]  # same path structure: same leaf paths
-        leaves = self.walk(specs, f"{ds_path}/{DATASET_DIRNAME}/feature", compare if prune else None)
+        if device_walk is None:
+            device_walk = D.DEVICE_WALK
+        depth = None
+        if prune and engine is not None and device_walk and metas[compare[0]][3] is not None:
+            depth = PathEncoding.from_dict(metas[compare[0]][3]).levels
+        leaves = self.walk(specs, f"{ds_path}/{DATASET_DIRNAME}/feature", compare if prune else None,
+                           engine=engine if depth is not None else None, depth=depth, deltas=D.DEVICE_DELTAS)
         return [self._version(ds_path, m, lv, prune) if m is not None else None for m, lv in zip(metas, leaves)]
 
     def dataset_version(self, spec, ds_path):
         """DatasetVersion of ``ds_path`` at commit/tree ``spec``, or None if absent."""
         return self.dataset_versions([spec], ds_path)[0]
 
-    def diff_versions(self, base, target, ds_path):
+    def diff_versions(self, base, target, ds_path, engine=None, device_walk=None):
         """(old, new) DatasetVersions for a diff of two revisions, pruned to their changed subtrees"""
-        return tuple(self.dataset_versions([base, target], ds_path, compare=(0, 1)))
+        return tuple(self.dataset_versions([base, target], ds_path, compare=(0, 1), engine=engine, device_walk=device_walk))
 
-    def merge_versions(self, ancestor, ours, theirs, ds_path):
+    def merge_versions(self, ancestor, ours, theirs, ds_path, engine=None, device_walk=None):
         """(ancestor, ours, theirs) DatasetVersions pruned to the subtrees where ours and theirs
         differ (elsewhere libgit2's rule takes ours unchanged)"""
-        return tuple(self.dataset_versions([ancestor, ours, theirs], ds_path, compare=(1, 2)))
+        return tuple(self.dataset_versions([ancestor, ours, theirs], ds_path, compare=(1, 2), engine=engine,
+                                           device_walk=device_walk))

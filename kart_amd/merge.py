@@ -282,7 +282,7 @@ def merge_repo(engine, repo, ancestor, ours, theirs):
     parts = []
     for ds in ds_paths:
         pre = f"{ds}/.table-dataset/feature/"
-        vers = repo.merge_versions(*specs, ds)  # pruned to the subtrees where ours and theirs differ
+        vers = repo.merge_versions(*specs, ds, engine=engine)  # pruned to the subtrees where ours and theirs differ
 
         def ours_leaves(pre=pre):
             (lv,) = repo.walk([ours], pre.rstrip("/"))

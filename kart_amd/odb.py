@@ -92,7 +92,7 @@ class ObjectDB:
 
     def set_option(self, name, value):
         """an option of the object store (kd_odb_set_option: ``zlib`` 1 inflates with zlib even when
-        libdeflate is present); kept across reopens"""
+        libdeflate is present; ``walk_batch_bytes`` the batch size of walk_device); kept across reopens"""
         with self._lock:
             N.check(self.L.kd_odb_set_option(self._h, name.encode(), int(value)), "kd_odb_set_option")
             self._opts[name] = int(value)
@@ -247,6 +247,30 @@ class ObjectDB:
         with self._lock:
             N.check(self.L.kd_walk(self._h, b"".join(roots), k, subpath.encode(), c0, c1, threads, outs), "kd_walk")
         return [_take_leaves(self.L, outs[i]) for i in range(k)]
+
+    WALK_STATS = ("tasks", "device_tasks", "host_tasks", "trees", "device", "host", "fixups", "compressed", "deltas",
+                  "batches", "expand_us", "batch_us", "plan_us", "gather_us", "read_device_us", "join_upload_us",
+                  "join_kernels_us", "download_us", "stitch_us", "host_walk_us", "call_us")
+
+    def walk_device(self, engine, roots, subpath="", compare=None, depth=0, deltas=False, threads=0):
+        """``walk`` with its lowest level on the GPU (kd_walk_device): the same Leaves, byte for byte.  The
+        host expands ``depth`` levels below the walked tree (a dataset's ``PathEncoding.levels``); the
+        subtrees left there are read through the batched device read (``deltas=True``: delta-compressed
+        trees rebuilt on the GPU too) and parsed, joined and pruned by kd_tree_join_batch.  Returns
+        ([Leaves], stats): ``tasks`` = ``device_tasks`` + ``host_tasks`` (a task the device refuses is
+        walked here as before), ``trees`` unique trees requested, the read's ``device`` / ``host`` /
+        ``fixups`` / ``compressed`` / ``deltas`` summed over ``batches``, and the phases in microseconds
+        (kartdiff.h, kd_walk_device: stats [10..19])."""
+        roots = [oid_bytes(r) for r in roots]
+        k = len(roots)
+        c0, c1 = compare if compare is not None else (N.KD_WALK_ALL, N.KD_WALK_ALL)
+        outs = (ctypes.POINTER(N.KdLeaves) * k)()
+        stats = np.zeros(N.KD_WD_STATS, np.uint64)
+        with self._lock:
+            N.check(self.L.kd_walk_device(engine.ctx, self._h, b"".join(roots), k, subpath.encode(), c0, c1, threads, int(depth),
+                                          N.KD_RBD_DELTAS if deltas else 0, outs, stats.ctypes.data_as(N.c_u64p)),
+                    "kd_walk_device")
+        return [_take_leaves(self.L, outs[i]) for i in range(k)], dict(zip(self.WALK_STATS, map(int, stats)))
 
     def tree_entries(self, oid):
         """one tree level: [(mode, type name, oid hex, name)] in git order"""
