@@ -379,7 +379,12 @@ int kd_sf_index_free(kd_sf_index* index);
  * enc/enc_ok (optional, NULL): the new side's spatial-index envelope (EnvelopeEncoder, bits/2
  * bytes per delta), as kd_envelopes computes it.  pairs = (old blob | KD_NONE, new blob | KD_NONE)
  * per delta — classify2's delta list with the arenas indexed by sorted entry.  With d_n the count
- * is read on the device (pairs and outputs device memory, n = capacity).  match must be 2-B aligned. */
+ * is read on the device (pairs and outputs device memory, n = capacity: an upper bound of the
+ * count, the kernels do not clamp).  match must be 2-B aligned.
+ * Validation: kd_geom_filter locates the geometry value in a blob and reads nothing after that
+ * value's last byte.  A blob malformed only behind it (trailing bytes, a truncated later value) is
+ * answered as its well-formed twin; damage at or before that byte is 3 FALLBACK.  The heads forms
+ * (kd_geom_heads validates the whole blob, as msgpack.unpackb does) answer 3 for both. */
 #define KD_GF_RECT 0x1u /* the filter geometry is its own envelope (an axis-aligned rectangle) */
 /* kd_geom_filter_heads / kd_geom_filter_deltas: the heads are already in delta order — heads_old[d] /
  * heads_new[d] belong to delta d (an absent side's slot is never read), as the drop-in's blob reader

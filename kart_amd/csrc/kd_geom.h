@@ -144,7 +144,9 @@ __device__ __forceinline__ bool env_fast(const u32 r[11], u64 len, int& rc, doub
     const u32 f = h >> 24;
     pc = -1;
     if ((h & 0xFFFFFFu) != 0x005047u || (f & 0x20)) { rc = -1; return true; }  // 'G' 'P' version 0
-    if (f & 0x10) { rc = 0; return true; }  // empty: no envelope or point read
+    // empty: no envelope or point read (a value shorter than the 8-byte header is malformed, as in
+    // gpkg_env, whatever its flags say; the other ways out of here refuse such a value already)
+    if (f & 0x10) { rc = len < 8 ? -1 : 0; return true; }
     const int et = (f >> 1) & 7;
     if (et > 1) return false;
     const bool le = f & 1;

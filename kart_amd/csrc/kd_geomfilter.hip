@@ -24,7 +24,9 @@
 // Layout: one lane per delta, 4096 deltas per workgroup (16 rounds of 256).  The fast path loads
 // 112 bytes from each blob start (7 dwordx4, realigned with v_alignbyte) and decodes the common
 // shape — [legend str8(40), fixarray|array16 values, geometry first as ext8/16/32 'G'] — from
-// registers; anything else takes the byte-wise decoder on global memory.
+// registers; anything else takes the byte-wise decoder on global memory.  Neither walks the blob
+// behind the geometry value: bytes after its last byte are not read, and a blob malformed only there
+// is answered as its well-formed twin (kd_geom_heads validates the whole blob: the heads forms refuse it).
 #include <cstdlib>
 #include <type_traits>
 
@@ -138,13 +140,20 @@ struct GeomLoc {
 };
 __device__ __noinline__ GeomLoc find_geom_slow(const u8* b, u64 len, const u32* s_leg, const i16* s_gidx, int n_leg) {
     const u8 *p = b, *e = b + len;
-    if (len < 2 || *p++ != 0x92) return GeomLoc{-1, 0, 0};
+    if (len < 2) return GeomLoc{-1, 0, 0};
+    // top level: an array of 2 in any header form (msgpack.unpackb takes them all)
+    const u8 t = *p++;
+    if (t == 0xdc && p + 2 <= e) { if (be_n(p, 2) != 2) return GeomLoc{-1, 0, 0}; p += 2; }
+    else if (t == 0xdd && p + 4 <= e) { if (be_n(p, 4) != 2) return GeomLoc{-1, 0, 0}; p += 4; }
+    else if (t != 0x92) return GeomLoc{-1, 0, 0};
+    if (p >= e) return GeomLoc{-1, 0, 0};
     // legend hex: a 40-byte str
     u32 sl;
     const u8 c = *p++;
     if ((c & 0xe0) == 0xa0) sl = c & 31;
     else if (c == 0xd9 && p < e) sl = *p++;
     else if (c == 0xda && p + 2 <= e) { sl = be_n(p, 2); p += 2; }
+    else if (c == 0xdb && p + 4 <= e) { sl = be_n(p, 4); p += 4; }
     else return GeomLoc{-1, 0, 0};
     if (sl != 40 || p + 40 > e) return GeomLoc{-1, 0, 0};
     const int l = leg_lookup_bytes(p, s_leg, n_leg);
@@ -267,7 +276,11 @@ __device__ __forceinline__ void decode_side(const GfArgs& a, int s, u32 bi, u64 
             if (gi < 0) { h.code = GF_MATCH; return; }  // this legend has no geometry column: value None
             if (gi == 0 && p > 0) {
                 const u32 w11 = rr[11];
-                const u32 v = p == 44 ? (w11 & 0xff) : ((w11 >> 16) & 0xff);
+                // (a values count of 0 — the header's low nibble, or bytes 44..45 of an array16 —
+                // leaves no geometry value at byte p: nothing is decided from what follows the
+                // header, and the byte-wise path refuses the blob)
+                const bool none = p == 44 ? (ah & 15) == 0 : (w11 & 0xffffu) == 0;
+                const u32 v = none ? 0u : p == 44 ? (w11 & 0xff) : ((w11 >> 16) & 0xff);
                 if (v == 0xc0) { h.code = GF_MATCH; return; }  // null geometry
                 // ext header bytes p+1 .. p+5 (p = 44: bytes 45..49, p = 46: 47..51)
                 const u32 x0 = p == 44 ? __builtin_amdgcn_alignbyte(rr[12], rr[11], 1)
