@@ -115,7 +115,7 @@ KD_DL_HD u32 next_op(const u8* d, u64 dlen, u64 base_len, u64 dst_len, u64 writt
 }  // namespace kd_dl
 
 // ---------------------------------------------------------------------------------------------
-// the chained form (library internal): what kd_odb.cpp's planner hands to kd_delta.hip
+// the chained form (library internal): what the planner (kd_odb_plan.cpp) hands to kd_delta.hip
 // ---------------------------------------------------------------------------------------------
 namespace kd {
 

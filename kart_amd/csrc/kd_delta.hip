@@ -2,7 +2,7 @@
 //
 // <- the blob read under the field diff on a repository that was cloned, gc'd or repacked: most feature
 // blobs are OFS_DELTA / REF_DELTA entries against an earlier version of the same feature.  The host
-// plans a batch into levels of a delta forest (kd_odb_read_batch_device_ex, kd_odb.cpp); k_inf_streams
+// plans a batch into levels of a delta forest (kd_odb_read_batch_device_ex, kd_odb_plan.cpp); k_inf_streams
 // inflates the chain bases and the delta payloads, this kernel patches one level per launch.
 //
 // k_dl_apply: DL_G = 16 lanes per item, four items per wave, 16 per workgroup of 256.  The decoder is
@@ -135,7 +135,7 @@ static int dl_launch(kd_ctx* ctx, const DlArgs& a, u32 level = 0) {
                   [&] { hipLaunchKernelGGL(k_dl_apply<CHAIN>, dim3((unsigned)nwg), dim3(DL_NT), 0, ctx->stream, a); });
 }
 
-// kd_odb_read_batch_device_ex's device half (kd_odb.cpp is host-only C++).  Everything but the arena is
+// kd_odb_read_batch_device_ex's device half (kd_odb_devread.cpp is host-only C++).  Everything but the arena is
 // a grow-only "dl.*" slot; every status comes back in one copy.  Returns with the results.
 int delta_read_from_host(kd_ctx* ctx, const DlPlan& p) {
     KD_HIP(hipSetDevice(ctx->device));

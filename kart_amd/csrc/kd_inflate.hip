@@ -3,7 +3,7 @@
 // <- the blob read under the field diff: every feature blob of an imported layer is its own deflate
 // stream in the pack (git fast-import --depth=0, kart/fast_import.py:204,273), a few hundred bytes
 // long.  The host finds the entries and ships the compressed bytes (kd_odb_read_batch_device,
-// kd_odb.cpp); this kernel inflates them into the arena + off[n+1] layout kd_fielddiff reads.
+// kd_odb_plan.cpp, kd_odb_devread.cpp); this kernel inflates them into the arena + off[n+1] layout kd_fielddiff reads.
 //
 // k_inf_streams: one lane per item, one wave per workgroup.  The decoder is kd_inflate.h (shared
 // with the host); a lane's Huffman state (KD_INF_WORDS = 204 words: canonical counts, symbols in
@@ -55,7 +55,7 @@ static int check_offsets(const u64* off, u64 n, const char* what) {
     return KD_OK;
 }
 
-// kd_odb_read_batch_device's device half (kd_odb.cpp is host-only C++): h_src (pinned, src_off[n] + 8
+// kd_odb_read_batch_device's device half (kd_odb_devread.cpp is host-only C++): h_src (pinned, src_off[n] + 8
 // bytes), the offsets and the kinds are uploaded into workspace slots, the items land in d_dst, whose
 // offsets d_dst_off receives; h_status <- the n status bytes.  Returns with the results.
 int inflate_from_host(kd_ctx* ctx, const uint8_t* h_src, const uint64_t* h_src_off, const uint8_t* h_kind, uint64_t n,

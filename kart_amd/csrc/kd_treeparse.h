@@ -6,7 +6,7 @@
 //   entry    <octal mode> SP <name> NUL <20 raw OID bytes>, repeated to the end of the object
 //   order    between non-tree entries: names ascending by unsigned bytewise compare, then length
 // The decoder defines the *device class* of a tree: the trees for which the device join is provably
-// kd_walk's.  It is stricter than kd_odb.cpp's parse_tree and never laxer — whatever it refuses goes
+// kd_walk's.  It is stricter than kd_odb_walk.cpp's parse_tree and never laxer — whatever it refuses goes
 // to the host walk, which then behaves as it always did:
 //   KD_TJ_EMODE   a mode byte that is no octal digit, no digits at all, more than 11 digits or a
 //                 value above 2^32 - 1 (parse_tree wraps), or the object ends inside the mode
@@ -231,7 +231,7 @@ KD_TJ_HD u32 task_status(const Trees<K>& T) {
     return st;
 }
 
-// Walk::join + Walk::pruned of kd_odb.cpp restricted to non-tree entries: the K entry lists merged by
+// Walk::join + Walk::pruned of kd_odb_walk.cpp restricted to non-tree entries: the K entry lists merged by
 // name; a name is dropped in every root when roots c0 and c1 agree on it (both lack it, or both have it
 // with equal mode and OID; c0 < 0: nothing is dropped); fn(r, entry) for every other entry of each root
 // that has it, in name order and within a name in root order.  The trees passed task_status; a tree

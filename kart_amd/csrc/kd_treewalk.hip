@@ -1,6 +1,6 @@
 // kd_treewalk.hip — kd_tree_join_batch: changed leaf trees parsed, joined and pruned on the GPU.
 //
-// <- the lowest level of a pruned walk (Walk::join + Walk::pruned, kd_odb.cpp) at a high edit rate:
+// <- the lowest level of a pruned walk (Walk::join + Walk::pruned, kd_odb_walk.cpp) at a high edit rate:
 // every leaf tree of both sides has changed, and each one is parsed and merge-joined entry by entry.
 // The trees arrive inflated in one arena (k_inf_streams / k_dl_apply put them there); a task names up
 // to three of them, one per root, and a path prefix.
