@@ -689,6 +689,30 @@ int64_t kd_pack_hash_keys(const uint8_t* paths, const uint64_t* path_off, uint64
  * through the inverse rank maps. */
 int kd_int_keys_to_pks(const uint64_t* keys, uint64_t n, int64_t* pks);
 
+/* -------- key packing and the side scan on the GPU -------- */
+/* kd_pack_int_keys / kd_pack_hash_keys and kd_keys_scan in one asynchronous call on device memory
+ * (Dataset3.decode_path_to_1pk, kart/dataset3.py:250-259, and the path encoders,
+ * kart/dataset3_paths.py:202-215,283-299, decoded by the same code as the host entries): a path arena
+ * d_paths with its offsets d_path_off [n+1] — what kd_tree_join_batch's device form writes — becomes
+ * d_keys [n] and d_status [n] (0 ok / 1 not packable / 2 pk outside [-2^63, 2^63); the key of a refused
+ * entry is 0), and *d_info: info = what kd_keys_scan returns for the keys as written, bad = the refused
+ * entries, first_bad = the smallest refused index (UINT64_MAX when bad == 0).  n == 0: ascending = 1,
+ * bad = 0, everything else of info zero.  Every pointer is device memory; no host wait, nothing read
+ * back.  levels / hex are the hash path structure (ignored for KD_KEY_INT); 64 or more bucket bits, a
+ * NULL pointer or another key_mode: KD_EINVAL.  The arena is read inside [off[0], off[n]) only (in
+ * aligned 16-byte pieces holding at least one such byte); an entry with off[i+1] < off[i], or outside
+ * that range, gets status 1 and is not read.  Options: kp_tile [KD_KP_TILE] 512 / 1024 entries per
+ * workgroup, kp_lds_bytes [KD_KP_LDS_BYTES] the largest tile staged in LDS (longer ones decode from
+ * HBM); read-only kp_hbm_tiles: the tiles of the last call that did. */
+typedef struct kd_keypack_info {
+    kd_keys_info info;
+    uint64_t bad;
+    uint64_t first_bad;
+} kd_keypack_info; /* 56 bytes */
+int kd_pack_keys_device(kd_ctx* ctx, const uint8_t* d_paths, const uint64_t* d_path_off, uint64_t n,
+                        uint32_t key_mode, int levels, int hex, uint64_t* d_keys, uint8_t* d_status,
+                        kd_keypack_info* d_info);
+
 /* -------- git object database + leaf walk (host, no GPU) -------- */
 /* Replaces libgit2's ODB and tree iteration under Dataset3 (kart/dataset3.py:26-35,225-231,
  * kart/base_dataset.py:230-265) and the subtree pruning of Tree.diff_to_tree

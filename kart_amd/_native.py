@@ -214,6 +214,15 @@ class KdKeysInfo(ctypes.Structure):
     ]
 
 
+class KdKeypackInfo(ctypes.Structure):
+    """kd_keypack_info (kd_pack_keys_device): the scan of the keys as written and the refused entries"""
+    _fields_ = [
+        ("info", KdKeysInfo),
+        ("bad", ctypes.c_uint64),
+        ("first_bad", ctypes.c_uint64),  # 2**64 - 1 when bad == 0
+    ]
+
+
 class KdDiffResult(ctypes.Structure):
     _fields_ = [
         ("n_insert", ctypes.c_uint64),
@@ -401,6 +410,11 @@ SIGNATURES = {
          ctypes.c_void_p, ctypes.c_void_p],
     ),
     "kd_int_keys_to_pks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "kd_pack_keys_device": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "kd_odb_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
     "kd_odb_close": (ctypes.c_int, [ctypes.c_void_p]),
     "kd_odb_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),

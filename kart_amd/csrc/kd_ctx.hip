@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "kd_internal.h"
+#include "kd_keypack.h"
 #include "kd_walkkey.h"
 
 namespace kd {
@@ -200,60 +201,6 @@ int prof_flush(kd_ctx* ctx) {
     return KD_OK;
 }
 
-// host-side key packing helpers
-static inline int b64v(u8 c) {
-    if (c >= 'A' && c <= 'Z') return c - 'A';
-    if (c >= 'a' && c <= 'z') return c - 'a' + 26;
-    if (c >= '0' && c <= '9') return c - '0' + 52;
-    if (c == '-') return 62;
-    if (c == '_') return 63;
-    return -1;
-}
-
-// pk (sign, magnitude) -> KD_KEY_INT walk key (kd_walkkey.h); 0 ok, 2 outside [-2^63, 2^63)
-static inline int int_key(bool neg, u64 mag, u64* key) {
-    if (neg ? mag > (1ull << 63) : mag >= (1ull << 63)) return 2;
-    *key = wk::int_key(neg ? (i64)(0 - mag) : (i64)mag);
-    return 0;
-}
-
-static int decode_int_name(const u8* s, int n, u64* key) {
-    u8 buf[16];
-    int o = 0, acc = 0, bits = 0;
-    for (int i = 0; i < n; i++) {
-        if (s[i] == '=') break;
-        int v = b64v(s[i]);
-        if (v < 0) return 1;
-        acc = (acc << 6) | v;
-        bits += 6;
-        if (bits >= 8) {
-            bits -= 8;
-            if (o >= 16) return 1;
-            buf[o++] = (u8)((acc >> bits) & 0xFF);
-        }
-    }
-    if (o < 2 || buf[0] != 0x91) return 1;
-    u8 t = buf[1];
-    int w = 0;
-    bool sgn = false;
-    u64 u = 0;
-    if (t <= 0x7f) { u = t; }
-    else if (t >= 0xe0) { sgn = true; u = (u64)(i64)(int8_t)t; }
-    else if (t >= 0xcc && t <= 0xcf) { w = 1 << (t - 0xcc); }
-    else if (t >= 0xd0 && t <= 0xd3) { w = 1 << (t - 0xd0); sgn = true; }
-    else return 1;
-    if (o != 2 + w) return 1;
-    if (w) {
-        for (int i = 0; i < w; i++) u = (u << 8) | buf[2 + i];
-        if (sgn) { int sh = 64 - 8 * w; u = (u64)(((i64)(u << sh)) >> sh); }
-    }
-    if (sgn) {
-        i64 v = (i64)u;
-        return int_key(v < 0, v < 0 ? (u64)(-(__int128)v) : (u64)v, key);
-    }
-    return int_key(false, u, key);
-}
-
 template <typename F>
 static void par_for(u64 n, F&& f) {
     unsigned nt = std::thread::hardware_concurrency();
@@ -268,12 +215,6 @@ static void par_for(u64 n, F&& f) {
         th.emplace_back([&f, a, b] { for (u64 i = a; i < b; i++) f(i); });
     }
     for (auto& t : th) t.join();
-}
-
-static inline u64 fnv1a64(const u8* p, u64 n) {
-    u64 h = 1469598103934665603ull;
-    for (u64 i = 0; i < n; i++) { h ^= p[i]; h *= 1099511628211ull; }
-    return h;
 }
 
 }  // namespace kd
@@ -325,6 +266,8 @@ const OptDef OPTS[] = {
     {"step_overlap_min", "KD_STEP_OVERLAP_MIN", nullptr, nullptr, &kd_opts::step_overlap_min},
     {"pkm_wave", "KD_PKM_WAVE", nullptr, &kd_opts::pkm_wave, nullptr},
     {"step_count", "KD_STEP_COUNT", nullptr, &kd_opts::step_count, nullptr},
+    {"kp_tile", "KD_KP_TILE", nullptr, &kd_opts::kp_tile, nullptr},
+    {"kp_lds_bytes", "KD_KP_LDS_BYTES", nullptr, &kd_opts::kp_lds_bytes, nullptr},
 };
 void opt_set(kd_opts& o, const OptDef& d, int64_t v) {
     if (d.i32) o.*(d.i32) = (int)v;
@@ -344,6 +287,7 @@ int kd_set_option(kd_ctx* ctx, const char* name, int64_t value) {
 
 int kd_get_option(kd_ctx* ctx, const char* name, int64_t* value) {
     KD_CHECK(ctx && name && value, "kd_get_option: NULL");
+    if (!strcmp(name, "kp_hbm_tiles")) return kd::keypack_hbm_tiles(ctx, value);  // read-only (kd_keypack.hip)
     for (const OptDef& d : OPTS)
         if (!strcmp(d.name, name)) {
             *value = d.i32 ? (int64_t)(ctx->opt.*(d.i32)) : (int64_t)(ctx->opt.*(d.u64));
@@ -520,15 +464,11 @@ int kd_prof_reset(kd_ctx* ctx) {
 int64_t kd_pack_int_keys(const uint8_t* names, const uint64_t* name_off, uint64_t n, uint64_t* keys,
                          uint8_t* status) {
     if (!names || !name_off || !keys || !status) { set_error("kd_pack_int_keys: NULL"); return KD_EINVAL; }
-    std::vector<u64> badc(1, 0);
     std::mutex m;
     u64 bad = 0;
-    par_for(n, [&](u64 i) {
-        u64 a = name_off[i], b = name_off[i + 1];
-        for (u64 j = b; j > a; j--)  // a relative path "c/c/c/c/<filename>": its filename
-            if (names[j - 1] == '/') { a = j; break; }
+    par_for(n, [&](u64 i) {  // (kd_keypack.h: the filename of a relative path "c/c/c/c/<filename>")
         u64 k = 0;
-        int st = (b - a > 24) ? 1 : decode_int_name(names + a, (int)(b - a), &k);
+        const int st = kp::int_entry(names + name_off[i], name_off[i + 1] - name_off[i], &k);
         keys[i] = k;
         status[i] = (u8)st;
         if (st) { std::lock_guard<std::mutex> g(m); bad++; }
@@ -542,36 +482,8 @@ int64_t kd_pack_hash_keys(const uint8_t* paths, const uint64_t* path_off, uint64
     std::mutex m;
     u64 bad = 0;
     par_for(n, [&](u64 i) {
-        const u8* s = paths + path_off[i];
-        u64 len = path_off[i + 1] - path_off[i];
-        u64 bucket = 0, pos = 0;
-        int bits = 0, st = 0;
-        for (int l = 0; l < levels && !st; l++) {
-            int seg = hex ? 2 : 1;
-            for (int c = 0; c < seg && !st; c++) {
-                if (pos >= len) { st = 1; break; }
-                u8 ch = s[pos++];
-                int v;
-                if (hex) {
-                    v = (ch >= '0' && ch <= '9') ? ch - '0' : (ch >= 'a' && ch <= 'f') ? ch - 'a' + 10 : -1;
-                    if (v < 0) { st = 1; break; }
-                    bucket = (bucket << 4) | (u64)v; bits += 4;
-                } else {
-                    v = b64v(ch);
-                    if (v < 0) { st = 1; break; }
-                    // the digit's ASCII rank: bucket order = git's tree order (kd_walkkey.h)
-                    bucket = (bucket << 6) | (u64)wk::T.rank[v]; bits += 6;
-                }
-            }
-            if (!st && (pos >= len || s[pos] != '/')) st = 1;
-            pos++;
-        }
         u64 k = 0;
-        if (!st) {
-            int low = 64 - bits;
-            u64 h = fnv1a64(s + pos, len - pos);
-            k = (bucket << low) | (h >> (64 - low));
-        }
+        const int st = kp::hash_entry(paths + path_off[i], path_off[i + 1] - path_off[i], levels, hex, &k);
         keys[i] = k;
         status[i] = (u8)st;
         if (st) { std::lock_guard<std::mutex> g(m); bad++; }

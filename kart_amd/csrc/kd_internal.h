@@ -95,6 +95,11 @@ struct kd_opts {
     // KD_PKM_WAVE: the bitmap pk order's scans in their LDS-free one-wave-per-chunk form: -1 on
     // kd_diff2_step's side stream only, 0 never, 1 always
     int pkm_wave = -1;
+    // KD_KP_TILE: entries per workgroup of kd_pack_keys_device's k_kp_pack, 512 or 1024 (kd_keypack.hip)
+    int kp_tile = 512;
+    // KD_KP_LDS_BYTES: the largest tile span k_kp_pack stages in LDS (at most 30720); a tile whose
+    // paths are longer decodes from HBM.  (Lowering it is how the tests reach that branch cheaply.)
+    int kp_lds_bytes = 30720;
 };
 
 struct kd_ctx {
@@ -246,6 +251,10 @@ struct InfArgs {
     u8* status;
 };
 int inflate_launch(kd_ctx* ctx, const InfArgs& a);
+
+// kd_keypack.hip: the tiles of the last kd_pack_keys_device call that decoded from HBM because their
+// paths did not fit the LDS budget (kd_get_option "kp_hbm_tiles"; waits for the stream)
+int keypack_hbm_tiles(kd_ctx* ctx, int64_t* value);
 
 // ---- classify2 (device form), kd_classify.hip ----
 // ordA / ordB (both or neither): the sides' OIDs and filename offsets are in another order, row

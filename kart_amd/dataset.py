@@ -59,6 +59,10 @@ DEVICE_DELTAS = os.environ.get("KD_DEVICE_DELTAS", "0") not in ("", "0")
 # on the GPU (ObjectDB.walk_device) when an engine is passed.  Off unless KD_DEVICE_WALK says otherwise
 # (DESIGN.md §3.7c); on that route delta-compressed trees follow DEVICE_DELTAS.
 DEVICE_WALK = os.environ.get("KD_DEVICE_WALK", "0") not in ("", "0")
+# DatasetVersion.pack: True = a side's join keys and their scan are made on the GPU (kd_pack_keys_device)
+# from one upload of its paths, offsets and OIDs when an engine is passed, and the side keeps those device
+# buffers.  Off unless KD_DEVICE_KEYS says otherwise; GPU_SORT_MIN does not gate it.
+DEVICE_KEYS = os.environ.get("KD_DEVICE_KEYS", "0") not in ("", "0")
 
 
 class Geometry(bytes):
@@ -176,10 +180,18 @@ class DatasetVersion:
     def packed(self):
         return self.pack()
 
-    def pack(self, engine=None):
+    def pack(self, engine=None, device_keys=None):
         """the side packed for the join (cached).  With a GPU engine and a large side the sort runs
-        on the GPU (kd_sort_side); the host parses the keys either way.  A GPU-packed side holds device
-        buffers of the engine that packed it: another engine, or that engine once closed, re-packs."""
+        on the GPU (kd_sort_side); the host parses the keys either way, unless ``device_keys`` (None:
+        ``DEVICE_KEYS``) is on: then, with an engine and at least one leaf, the keys are made on the GPU
+        too, whatever the side's size.  A GPU-packed side holds device buffers of the engine that packed
+        it: another engine, or that engine once closed, re-packs."""
+        if device_keys is None:
+            device_keys = DEVICE_KEYS
+        if self._packed is not None and self._packed.dev is not None:  # (a device_keys side: its keys are in HBM)
+            own = self._packed_by
+            if (engine is not None and own is not engine) or not getattr(own, "ctx", None):
+                self._packed = None
         if self._packed is not None and self._packed.dperm is not None and engine is not None:
             own = self._packed_by
             if own is not engine or not getattr(own, "ctx", None):
@@ -189,9 +201,10 @@ class DatasetVersion:
             if self.n == 0:
                 self._packed = packing.empty_side(self.encoding)
             else:
-                gpu = engine if self.n >= GPU_SORT_MIN and hasattr(engine, "ctx") else None
+                on_gpu = bool(device_keys) and hasattr(engine, "ctx")
+                gpu = engine if (self.n >= GPU_SORT_MIN or on_gpu) and hasattr(engine, "ctx") else None
                 self._packed = packing.pack_side(self.rel_paths, self.oids, self.encoding, rel_off=self.rel_off,
-                                                 engine=gpu)
+                                                 engine=gpu, device_keys=on_gpu)
                 self._packed_by = gpu
         return self._packed
 

@@ -102,6 +102,38 @@ class DevSide:
             self.name = DevBuf.from_numpy(engine, _nonempty(side.name, np.uint8))
             self.name_off = DevBuf.from_numpy(engine, side.name_off)
 
+    info = None  # from_leaves: the scan of the walk-order keys (_native.KdKeysInfo)
+
+    @classmethod
+    def from_leaves(cls, engine, d_paths, d_off, d_oid, n, encoding):
+        """A side born in HBM: ``d_paths`` / ``d_off`` (n + 1 uint64 offsets) / ``d_oid`` (n * 20 bytes) are
+        DevBufs holding one root's leaves as kd_tree_join_batch's device form (or an upload) lists them.
+        The keys and their scan are made on the device (Engine.pack_keys: 56 bytes come back); a side
+        ascending as walked becomes a DevSide over the given buffers (nothing is copied), any other a
+        DevPermSide sorted by packing.sort_on_device_perm on the keys already in HBM.  Either carries
+        ``info``.  packing.PackError, with parse_keys' and pack_side's texts, on a path the encoding cannot
+        pack and on a duplicate key."""
+        from . import packing
+
+        n = int(n)
+        keys, status, info, bad, first_bad = engine.pack_keys(d_paths, d_off, n, encoding)
+        if bad:
+            a, b = (int(x) for x in d_off.download(np.uint64, 2, 8 * first_bad))
+            path = d_paths.download(np.uint8, b - a, a).tobytes() if b > a else b""
+            raise packing.PackError(f"{bad} feature paths not packable, first: {path!r}")
+        status.free()
+        hashed = encoding.key_mode == N.KD_KEY_HASH
+        if info.ascending:
+            s = cls.__new__(cls)
+            s.n, s.key_mode, s.key, s.oid = n, encoding.key_mode, keys, d_oid
+            s.name, s.name_off = (d_paths, d_off) if hashed else (None, None)
+            s.info = info
+            return s
+        dp, _, _ = packing.sort_on_device_perm(engine, keys, d_oid, info, encoding, d_paths, d_off, n=n, mirror=False)
+        keys.free()
+        dp.info = info
+        return dp
+
     def kd_side(self):
         s = N.KdSide()
         s.n = self.n

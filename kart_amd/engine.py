@@ -449,6 +449,28 @@ class Engine:
             res.append((pa[:nb], po[:n + 1], oo[:n], mo[:n]))
         return res, count[:nt], status[:nt]
 
+    def pack_keys(self, d_paths, d_off, n, encoding):
+        """join keys and the side scan of a path arena that is in HBM (kd_pack_keys_device): ``d_paths`` /
+        ``d_off`` DevBufs (or device addresses) of the arena and its n + 1 uint64 offsets, ``encoding`` the
+        dataset's PathEncoding.  Returns (keys DevBuf uint64 [n], status DevBuf uint8 [n], KdKeysInfo of the
+        keys as written, bad, first_bad); the one read-back is the 56-byte info record."""
+        from .device import DevBuf
+
+        n = int(n)
+        hex_ = 1 if encoding.encoding == "hex" else 0
+        if encoding.key_mode == N.KD_KEY_HASH and ((hex_ and encoding.branches != 256) or (not hex_ and encoding.branches != 64)):
+            from .packing import PackError
+
+            raise PackError(f"unsupported path structure {encoding}")
+        keys, status, info = DevBuf(self, 8 * n), DevBuf(self, n), DevBuf(self, ctypes.sizeof(N.KdKeypackInfo))
+        N.check(self.L.kd_pack_keys_device(self.ctx, getattr(d_paths, "ptr", d_paths), getattr(d_off, "ptr", d_off), n,
+                                           int(encoding.key_mode), int(encoding.levels), hex_, keys.ptr, status.ptr,
+                                           info.ptr), "kd_pack_keys_device")
+        raw = info.download(np.uint8, ctypes.sizeof(N.KdKeypackInfo))
+        r = N.KdKeypackInfo.from_buffer_copy(raw.tobytes())
+        ki = N.KdKeysInfo.from_buffer_copy(bytes(r.info))
+        return keys, status, ki, int(r.bad), int(r.first_bad)
+
     def merge3(self, ancestor, ours, theirs, flags=0) -> Merge3Result:
         """three PackedSides -> conflicts / merge deltas in path order (kd_merge3; sides packed on the
         GPU with walk-order rows through kd_merge3_device_perm)"""

@@ -190,7 +190,7 @@ def _gather_names(paths, off, order, chunk=1 << 20):
 SEG_SORT_MAX = 512  # the longest leaf tree kd_sort_segmented_into orders (err 4 beyond)
 
 
-def sort_on_device_perm(engine, keys, oids, info, encoding, paths, off):
+def sort_on_device_perm(engine, keys, oids, info, encoding, paths, off, n=None, mirror=True):
     """GPU pack of a side whose walk order is not key order, late-materialised as bench.py times it:
     the per-leaf-tree sort (kd_sort_segmented_into, one kernel) — KD_KEY_HASH sides always try it (a
     leaf tree lists its entries in filename order, not FNV order), KD_KEY_INT sides when the host's
@@ -198,14 +198,20 @@ def sort_on_device_perm(engine, keys, oids, info, encoding, paths, off):
     trees) — else, or when a bucket is long or the buckets descend, the full radix sort of the
     compacted varying key bits (kd_sort_side_into, passes from kd_keys_scan, no OIDs moved).
     Returns (DevPermSide, sorted keys, order) — OIDs and filenames stay in walk order.  PackError on
-    duplicate keys."""
+    duplicate keys.
+
+    A side that is in HBM already (device.DevSide.from_leaves): ``keys``, ``oids``, ``paths`` and ``off``
+    may each be a DevBuf, which is used as it stands instead of an upload (``n`` entries; the walk-order
+    key buffer stays the caller's); ``mirror=False`` skips the host copies of the sorted keys and the
+    order (None in their place)."""
     import ctypes
 
     from . import shard
     from .device import DevBuf, DevPermSide
 
-    n = keys.shape[0]
-    dk_in = DevBuf.from_numpy(engine, keys)
+    keys_given = isinstance(keys, DevBuf)
+    n = int(n) if keys_given else keys.shape[0]
+    dk_in = keys if keys_given else DevBuf.from_numpy(engine, keys)
     dk, dord, flag = DevBuf(engine, 8 * n), DevBuf(engine, 4 * n), DevBuf(engine, 8)
     sorted_ok = False
     if encoding.key_mode == N.KD_KEY_HASH or 0 < info.seg_max <= SEG_SORT_MAX:
@@ -221,14 +227,17 @@ def sort_on_device_perm(engine, keys, oids, info, encoding, paths, off):
                                            ctypes.byref(info)), "kd_sort_side_into")
         if int(flag.download(np.uint32, 1)[0]):
             raise PackError("duplicate join keys within one side")
-    dk_in.free()
+    if not keys_given:
+        dk_in.free()
     flag.free()
-    do = DevBuf.from_numpy(engine, oids.reshape(-1))
+    do = oids if isinstance(oids, DevBuf) else DevBuf.from_numpy(engine, oids.reshape(-1))
     name = name_off = None
     if encoding.key_mode == N.KD_KEY_HASH:
-        name = DevBuf.from_numpy(engine, paths if paths.size else np.zeros(1, np.uint8))
-        name_off = DevBuf.from_numpy(engine, off)
+        name = paths if isinstance(paths, DevBuf) else DevBuf.from_numpy(engine, paths if paths.size else np.zeros(1, np.uint8))
+        name_off = off if isinstance(off, DevBuf) else DevBuf.from_numpy(engine, off)
     dp = DevPermSide(engine, n, encoding.key_mode, dk, do, dord, name, name_off)
+    if not mirror:
+        return dp, None, None
     return dp, dk.download(np.uint64, n), dord.download(np.uint32, n).astype(np.int64)
 
 
@@ -250,19 +259,58 @@ def sort_on_device(engine, keys, oids):
     return dk, do, dord
 
 
-def pack_side(rel_paths, oids, encoding: PathEncoding, rel_off=None, engine=None):
+def _pack_side_device(engine, paths, off, oids, encoding):
+    """pack_side's ``device_keys`` route: paths, offsets and OIDs go up once, the keys and the scan are
+    made in HBM (device.DevSide.from_leaves), and only ``key`` and ``order`` are mirrored to the host"""
+    from .device import DevBuf, DevSide
+
+    n = len(off) - 1
+    t0 = time.perf_counter()
+    d_paths = DevBuf.from_numpy(engine, paths if paths.size else np.zeros(1, np.uint8))
+    d_off = DevBuf.from_numpy(engine, off)
+    d_oid = DevBuf.from_numpy(engine, oids.reshape(-1))
+    t1 = time.perf_counter()
+    ds = DevSide.from_leaves(engine, d_paths, d_off, d_oid, n, encoding)
+    t2 = time.perf_counter()
+    keys = ds.key.download(np.uint64, n)
+    side = PackedSide(key=keys, oid=oids, key_mode=encoding.key_mode, order=np.arange(n, dtype=np.int64),
+                      encoding=encoding, info=ds.info)
+    if isinstance(ds, DevSide):  # ascending as walked
+        side.dev = (ds.key, ds.oid)
+        sort_on = "none"
+        if encoding.key_mode == N.KD_KEY_HASH:
+            side.name, side.name_off = paths, off
+    else:
+        side.dperm = ds
+        side.order = ds.order.download(np.uint32, n).astype(np.int64)
+        sort_on = "gpu"
+        if encoding.key_mode == N.KD_KEY_HASH:  # the walk-order arena: the join reads it through the order
+            side.name, side.name_off = paths, off
+    side.timing = {"upload_s": t1 - t0, "parse_s": t2 - t1, "sort_s": time.perf_counter() - t2, "sort_on": sort_on,
+                   "keys_on": "gpu"}
+    return side
+
+
+def pack_side(rel_paths, oids, encoding: PathEncoding, rel_off=None, engine=None, device_keys=False):
     """Pack leaves: rel_paths = list[str] (relative to feature/) or a uint8 arena with
     ``rel_off``; oids = uint8 [n, 20].  Returns PackedSide.  Raises PackError on paths that are
     not valid for the encoding (the caller falls back to the reference path).
 
     With an ``engine`` the sort runs on the GPU (kd_sort_side) and the side keeps its device copy
-    (``side.dev``), which the engine's diffs then use without another upload."""
+    (``side.dev``), which the engine's diffs then use without another upload.
+
+    ``device_keys`` (with an engine and at least one leaf): the keys and their scan are made on the GPU
+    too (kd_pack_keys_device) from one upload of paths, offsets and OIDs.  The side equals the host
+    route's in every host field and keeps its device buffers: ``dev`` when the walk order is key
+    order, ``dperm`` otherwise."""
     if rel_off is None:
         paths, off = _arena(rel_paths)
     else:
         paths, off = np.ascontiguousarray(rel_paths, np.uint8), np.ascontiguousarray(rel_off, np.uint64)
     n = len(off) - 1
     oids = np.ascontiguousarray(oids, np.uint8).reshape(n, 20)
+    if device_keys and engine is not None and n > 0:
+        return _pack_side_device(engine, paths, off, oids, encoding)
     t0 = time.perf_counter()
     keys = parse_keys(paths, off, encoding)
     info = keys_scan(keys, encoding.key_mode)
